@@ -6,15 +6,19 @@ Workload (BASELINE.json configs[1], "C2"): psnr_256 semantics — lambda=256,
 MSE distortion, Laplacian conditional, 192/192 channels, fp32, batch 32 per
 GPU (weak scaling: the per-GPU batch stays 32 as N grows).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
         --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` times the dominant kernel (the
+Rank 0 prints ONE JSON line.  A plain run does only what the headline figure
+needs: set up, warm up, time the K steps, write the last step's outputs when
+--dump-outputs is given, print the line.  `--full` adds the measurements that
+take runs of their own: `roofline` times the dominant kernel (the
 implicit-GEMM conv, measured on the analysis transform's 128->64 5x5 192->192
-layer) with events on the launch stream; `cpu_baseline` times the CPU oracle
-(oracle/ref_cpu.py, a restatement of the reference path) on a bounded sample
-on this host.
+layer) with events on the launch stream, `optimizer_step_ms` times the
+optimizer, and `cpu_baseline` times the CPU oracle (oracle/ref_cpu.py, a
+restatement of the reference path) on a bounded sample on this host; without
+`--full` those three fields are null.
 """
 import argparse
 import json
@@ -288,6 +292,45 @@ def cpu_baseline(seconds_target=12.0):
                       f"(oracle/ref_cpu.py, torch CPU, {threads} threads)"}
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6       # --dump-outputs: everything written, in all
+DUMP_IMAGE_ELEMS = 8 * 2 ** 20      # x_tilde: whole up to this many elements (C2's 6.3 M fit), else a sample
+DUMP_GRAD_ELEMS = 2 ** 18           # each gradient: whole up to this many elements, else a sample
+
+
+def _dump_sample(t, max_elems, seed):
+    """`t` as a float32 host array: whole when it has at most `max_elems` elements, otherwise the
+    elements at a fixed index set (seeded, sorted, the same from run to run and build to build)."""
+    t = t.detach()
+    if t.numel() > max_elems:
+        g = torch.Generator().manual_seed(seed)
+        idx = torch.randint(0, t.numel(), (max_elems,), generator=g).sort().values
+        t = t.reshape(-1)[idx.to(t.device)]
+    return t.to(device="cpu", dtype=torch.float32).numpy()
+
+
+def dump_outputs(out_dir, x_tilde, losses, named_params):
+    """--dump-outputs: what the last timed step handed its caller, as <name>.npy (float32):
+    `x_tilde` (eager steps; a hipGraph replay returns the losses only), one `loss.<name>` per
+    entry of the loss dict, one `grad.<parameter name>` per parameter.  Large arrays are sampled
+    (_dump_sample); the total stays under DUMP_MAX_BYTES."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {}
+    if x_tilde is not None:
+        arrays["x_tilde"] = _dump_sample(x_tilde, DUMP_IMAGE_ELEMS, 0)
+    for k, v in losses.items():
+        arrays[f"loss.{k}"] = v.detach().to(device="cpu", dtype=torch.float32).reshape(1).numpy()
+    for i, (name, p) in enumerate(named_params):
+        if p.grad is not None:
+            arrays[f"grad.{name}"] = _dump_sample(p.grad, DUMP_GRAD_ELEMS, 1 + i)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit(f"bench.py: --dump-outputs would write {total} bytes > {DUMP_MAX_BYTES}")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def _free_port():
     import socket
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
@@ -346,8 +389,14 @@ def main():
                     help="BASELINE.json workload (C2 = the metric's; default)")
     ap.add_argument("--batch", type=int, default=None, help="images per GPU (default: the config's)")
     ap.add_argument("--size", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (x_tilde, the losses, the "
+                         "gradients; float32, large arrays as a fixed seeded sample) to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the dominant kernel's roofline, the "
+                         "optimizer step and the CPU baseline (null in a plain run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: leave the roofline out")
     ap.add_argument("--profile-step-only", action="store_true",
                     help="only warmup+timed steps (for rocprofv3 runs)")
     ap.add_argument("--graph", action="store_true",
@@ -389,22 +438,25 @@ def main():
 
         def step():
             model.zero_grad(set_to_none=True)
-            _, losses = model(x)
+            x_tilde, losses = model(x)
             losses["total_loss"].backward()
-            return losses
+            return x_tilde, losses
         mode = ("eager, DDP 12 MB buckets" if dist else "eager") + (
             ", hyperprior on the main stream" if args.serial_hyperprior else ", hyperprior on a side stream")
     else:
         # fwd + loss + bwd captured once into a hipGraph and replayed (one GPU)
-        step = TrainStep(model, x, graph=True)
+        graph_step = TrainStep(model, x, graph=True)
+
+        def step():
+            return None, graph_step()
         mode = "hipGraph"
 
     live = None
-    if not args.graph and args.config in ROOFLINE_CONFIGS and not args.no_roofline:
+    if args.full and not args.graph and args.config in ROOFLINE_CONFIGS and not args.no_roofline:
         core = getattr(model, "module", model)
         live = LiveLaunchTimer(core.analysis_transform.layers[2])
     for _ in range(args.warmup):
-        losses = step()
+        x_tilde, losses = step()
     torch.cuda.synchronize()
     D.barrier(dev)
     torch.cuda.synchronize()
@@ -412,7 +464,7 @@ def main():
         live.on = True
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        losses = step()
+        x_tilde, losses = step()
     torch.cuda.synchronize()
     if live is not None:
         live.on = False
@@ -421,22 +473,24 @@ def main():
     dname = conf["loss"][0]
     avg = D.mean_over_ranks({"bpp": losses["bpp"], dname: losses[dname]}, dev)
     bpp, dist_val = avg["bpp"], avg[dname]
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, x_tilde, losses, list(getattr(model, "module", model).named_parameters()))
     if args.profile_step_only:
         if rank == 0:
             print(json.dumps({"ms_per_step": 1e3 * elapsed / args.steps}))
         D.teardown()
         return
 
-    opt_ms = optimizer_step_ms(step.model if hasattr(step, "model") else model, dev)
+    opt_ms = optimizer_step_ms(model, dev) if args.full else None
     images = args.batch * world * args.steps
     value = images / elapsed
     ms = 1e3 * elapsed / args.steps
     roof = None
-    if not args.no_roofline and args.config in ROOFLINE_CONFIGS:
+    if args.full and not args.no_roofline and args.config in ROOFLINE_CONFIGS:
         roof = dominant_kernel_roofline(dev, live_ms=live.ms() if live else None,
                                         live_launches=len(live.pairs) if live else 0, math=conf["math"])
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C2":
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "C2":
         cpu = cpu_baseline()
     if rank == 0:
         # model FLOPs per image (3 x forward MACs x 2), x4 per 512^2 image

@@ -20,15 +20,36 @@ def pytest_configure(config):
     config.addinivalue_line("filterwarnings", "error:(?s).*AccumulateGrad node's stream does not match")
 
 
+class _Golden:
+    """The arrays of one golden case: <name>.npz and, where the case is too large for one
+    committed file (1 MiB), the rest of its arrays in <name>.partN.npz (tools/gen_golden.py)."""
+
+    def __init__(self, parts):
+        self._parts = parts
+        self.files = [k for z in parts for k in z.files]
+        assert len(self.files) == len(set(self.files)), "an array stored twice"
+
+    def __getitem__(self, key):
+        for z in self._parts:
+            if key in z.files:
+                return z[key]
+        raise KeyError(key)
+
+    def __contains__(self, key):
+        return key in self.files
+
+
 def load_golden(name):
-    d = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
+    paths = [os.path.join(GOLDEN, name + ".npz")] + sorted(glob.glob(os.path.join(GOLDEN, name + ".part[0-9].npz")))
+    d = _Golden([np.load(p, allow_pickle=False) for p in paths])
     meta = json.loads(str(d["meta"]))
     return meta, d
 
 
 def golden_names(prefix=""):
     return sorted(os.path.basename(p)[:-4]
-                  for p in glob.glob(os.path.join(GOLDEN, prefix + "*.npz")))
+                  for p in glob.glob(os.path.join(GOLDEN, prefix + "*.npz"))
+                  if ".part" not in os.path.basename(p))
 
 
 def params_of(d):
