@@ -179,12 +179,33 @@ SIGNATURES = {
                               c_float, c_float, c_void, c_void, c_void, c_void, c_void, c_void, c_size, c_void]),
     "ic_sqdiff_fwd": (c_int, [c_void, c_void, c_ll, c_void, c_void]),
     "ic_sqdiff_bwd": (c_int, [c_void, c_void, c_void, c_ll, c_void, c_void, c_void]),
+    # entropy coder (include/imgcomp.h ic_codec_*; ic_version 4)
+    "ic_codec_symbolize": (c_int, [c_void, c_ll, c_void, c_void, P(c_int), c_void]),
+    "ic_codec_scale_index": (c_int, [c_void, c_ll, P(c_float), c_int, c_void, c_void]),
+    "ic_codec_build_tables": (c_int, [c_void, c_int, c_int, c_void, c_void]),
+    "ic_codec_chunks": (c_ll, [c_ll, c_int]),
+    "ic_codec_encode_ws": (c_size, [c_ll, c_int]),
+    "ic_codec_compact_bytes": (c_size, [c_ll, c_int]),
+    "ic_codec_encode": (c_int, [c_void, c_ll, c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_size, c_void,
+                                c_void]),
+    "ic_codec_compact": (c_int, [c_void, c_void, c_ll, c_int, c_void, c_size, c_void]),
+    "ic_codec_decode": (c_int, [c_void, c_size, c_ll, c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_void]),
 }
 
 _lib = None
 _load_error = None
 TORCH_OPS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libimgcomp_torch.so")
 _ops = None
+_codec_ops = None
+
+
+def codec_ops():
+    """torch.ops.imgcomp_codec (the entropy coder's ops, registered by the same library as ops())."""
+    global _codec_ops
+    if _codec_ops is None:
+        ops()
+        _codec_ops = torch.ops.imgcomp_codec
+    return _codec_ops
 
 
 def ops():

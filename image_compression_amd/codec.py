@@ -1,0 +1,231 @@
+"""The compressed container of `Compressor2018.compress` / `decompress`, and the specification of
+the rANS bitstream inside it (kernels: csrc/codec.hip, `ic_codec_*`).  Host code only: nothing
+here launches a kernel, and `parse` validates a buffer completely before the caller launches any.
+
+Bitstream of one tensor
+-----------------------
+Symbols.  The tensor's eval-mode quantization q = rint(x) as integers, flattened in (n, h, w, c)
+order (channel fastest).  K = kmax = max |q| of the tensor, K <= 2047; symbol index j = q + K in
+[0, 2K].
+
+Tables.  A table has `rows` rows of 2K+2 unsigned cumulative counts: cdf[0] = 0 < cdf[1] < ... <
+cdf[2K+1] = 65536.  Symbol j has start = cdf[j], freq = cdf[j+1] - cdf[j] >= 1.  The row of symbol
+number i (its position in the flattened tensor) is i % C for z (one row per channel: the factorized
+prior) and index(sigma_i) for y, where index(s) = the number of midpoints strictly below s, the
+midpoints being m_t = float32(sqrt(S_t * S_{t+1})) of the L log-spaced scales
+S_t = exp(ln(scale_min) + t * (ln(scale_max) - ln(scale_min)) / (L - 1)) computed in float64, and the
+comparison s > m_t made in float32.  Row t of the y table is the conditional model's pmf at scale
+float32(S_t).  How a pmf becomes counts is DESIGN.md's table rule; the coder only needs the
+properties above.
+
+Chunks.  The symbols are cut into chunks of 64 * R consecutive symbols (R = steps_per_chunk; the last
+chunk may be shorter).  Symbol i of a chunk (i counted from the chunk's first symbol) belongs to
+lane i % 64 and step i // 64; the last step of a chunk may hold fewer than 64 symbols (lanes
+0 .. m-1).  Each lane is an independent rANS coder: 32-bit state x in [2^16, 2^32), precision 16,
+16-bit renormalisation words.
+
+Encoding a chunk.  Every lane starts at x = 2^16.  Steps are taken from the last to the first.  At a
+step, a lane that holds a symbol (start, freq):
+    if x >= freq * 2^16:  emit the word x & 0xFFFF;  x >>= 16          (at most once)
+    x = (x // freq) * 2^16 + (x % freq) + start
+Decoding reads the words forward, so the word sequence of a chunk is defined by the decoder's order:
+ascending step, and within a step ascending lane among the lanes that emitted at that step.  (The
+encoder, running backwards, fills its buffer from the end.)
+
+Chunk bytes.  64 final encoder states as little-endian uint32, lane 0 first (256 bytes, the fixed
+cost per chunk, written for idle lanes too), then the words as little-endian uint16 in the order
+above.  A chunk's length is 256 + 2 * (number of words) bytes, at most 256 + 2 * 64 * R.
+
+Decoding a chunk.  Lane l starts at the l-th state.  Steps ascend; at a step a lane that holds a
+symbol:
+    slot = x & 0xFFFF;  j = the index with cdf[j] <= slot < cdf[j+1] in the symbol's row
+    x = freq * (x >> 16) + slot - start
+    if x < 2^16:  x = (x << 16) | next word                            (at most once)
+where the lanes that refill at a step take consecutive words in ascending lane order.  A word past
+the chunk's end reads as 0.  The symbol is q = j - K.
+
+Payload.  The chunks back to back, in order; the chunk lengths are kept beside it (uint32 each).
+
+Container (little endian), one call = one batch = one bytes object
+-------------------------------------------------------------------
+    magic "ICRA", u16 format version (1), u8 arithmetic tag (index of COMPUTE_DTYPE in
+    COMPUTE_DTYPES), u8 conditional kind (0 Laplace, 1 Gauss), u32 ABI version (ic_version()),
+    u32 N, H, W (image batch), u32 latent channels (y), u32 hyper channels (z),
+    u32 L, f64 scale_min, f64 scale_max, u32 R, u32 kmax_z, u32 kmax_y,
+    u64 symbols of z, u64 symbols of y, u32 chunks of z, u32 chunks of y,
+    chunk lengths of z (u32 each), chunk lengths of y, payload of z, payload of y.
+y has N x latent x H/16 x W/16 symbols, z N x hyper x H/64 x W/64.
+"""
+import math
+import struct
+from dataclasses import dataclass
+
+import numpy as np
+
+MAGIC = b"ICRA"
+FORMAT_VERSION = 1
+KMAX_LIMIT = 2047          # IC_CODEC_KMAX: 2K+1 <= 4095 counts of >= 1 inside a 16-bit total
+MAX_SCALES = 256           # IC_CODEC_MAXL: rows are uint8
+MAX_STEPS = 65536          # IC_CODEC_MAXR
+PRECISION = 16
+CHUNK_HEAD = 256           # 64 lanes x 4 bytes of state
+COMPUTE_DTYPES = ("fp32_split", "fp32", "bf16")
+Y_DOWN, Z_DOWN = 16, 64    # image pixels per latent / hyper-latent sample, each way
+
+_HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQII")
+
+
+@dataclass
+class Header:
+    N: int
+    H: int
+    W: int
+    latent_channels: int
+    hyper_channels: int
+    kind: int
+    compute_dtype: str
+    abi: int
+    L: int
+    scale_min: float
+    scale_max: float
+    R: int
+    kmax_z: int
+    kmax_y: int
+
+    @property
+    def z_shape(self):
+        return (self.N, self.hyper_channels, self.H // Z_DOWN, self.W // Z_DOWN)
+
+    @property
+    def y_shape(self):
+        return (self.N, self.latent_channels, self.H // Y_DOWN, self.W // Y_DOWN)
+
+    @property
+    def nsym_z(self):
+        return int(np.prod(self.z_shape, dtype=np.int64))
+
+    @property
+    def nsym_y(self):
+        return int(np.prod(self.y_shape, dtype=np.int64))
+
+
+def num_chunks(nsym, R):
+    return -(-int(nsym) // (64 * int(R)))
+
+
+def scale_table(L, scale_min, scale_max):
+    """(scales float32[L], midpoints float32[L-1]) of the log-spaced scale table, from float64."""
+    lo, hi = math.log(float(scale_min)), math.log(float(scale_max))
+    s = [math.exp(lo + t * (hi - lo) / (L - 1)) for t in range(L)] if L > 1 else [float(scale_min)]
+    mids = [math.sqrt(s[t] * s[t + 1]) for t in range(L - 1)]
+    return np.asarray(s, dtype=np.float32), np.asarray(mids, dtype=np.float32)
+
+
+def fixed_bytes(h):
+    """The bytes of a container that do not depend on the symbols: header, length tables and the
+    256 bytes of lane states per chunk."""
+    nc = num_chunks(h.nsym_z, h.R) + num_chunks(h.nsym_y, h.R)
+    return _HEAD.size + 4 * nc + CHUNK_HEAD * nc
+
+
+def _check_header(h):
+    if h.compute_dtype not in COMPUTE_DTYPES:
+        raise ValueError(f"codec: unknown COMPUTE_DTYPE {h.compute_dtype!r}")
+    if h.kind not in (0, 1):
+        raise ValueError(f"codec: unknown conditional kind {h.kind}")
+    if min(h.N, h.H, h.W, h.latent_channels, h.hyper_channels) < 1:
+        raise ValueError("codec: empty batch shape")
+    if h.H % Z_DOWN or h.W % Z_DOWN:
+        raise ValueError(f"codec: image size {h.H}x{h.W} is not a multiple of {Z_DOWN}")
+    if not 1 <= h.L <= MAX_SCALES:
+        raise ValueError(f"codec: {h.L} scales (1..{MAX_SCALES})")
+    if not (math.isfinite(h.scale_min) and math.isfinite(h.scale_max) and 0.0 < h.scale_min
+            and (h.scale_min < h.scale_max or h.L == 1)):
+        raise ValueError(f"codec: bad scale range [{h.scale_min}, {h.scale_max}]")
+    if not 1 <= h.R <= MAX_STEPS:
+        raise ValueError(f"codec: steps_per_chunk {h.R} (1..{MAX_STEPS})")
+    for name, k in (("kmax_z", h.kmax_z), ("kmax_y", h.kmax_y)):
+        if not 0 <= k <= KMAX_LIMIT:
+            raise ValueError(f"codec: {name} = {k} exceeds the coder's limit of {KMAX_LIMIT}")
+
+
+def _check_lengths(name, lens, nsym, R):
+    if len(lens) != num_chunks(nsym, R):
+        raise ValueError(f"codec: {len(lens)} {name} chunk lengths for {nsym} symbols at R = {R}")
+    per = 64 * R
+    for c, n in enumerate(lens.tolist()):
+        words = min(per, nsym - c * per)
+        if n < CHUNK_HEAD or n % 2 or n > CHUNK_HEAD + 2 * words:
+            raise ValueError(f"codec: {name} chunk {c} of {words} symbols cannot be {n} bytes long")
+
+
+def pack(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object from the header, the two chunk-length tables and the two payloads."""
+    _check_header(h)
+    lens_z = np.ascontiguousarray(lens_z, dtype="<u4")
+    lens_y = np.ascontiguousarray(lens_y, dtype="<u4")
+    payload_z, payload_y = bytes(payload_z), bytes(payload_y)
+    _check_lengths("z", lens_z, h.nsym_z, h.R)
+    _check_lengths("y", lens_y, h.nsym_y, h.R)
+    if int(lens_z.sum(dtype=np.uint64)) != len(payload_z) or int(lens_y.sum(dtype=np.uint64)) != len(payload_y):
+        raise ValueError("codec: chunk lengths do not add up to the payload")
+    head = _HEAD.pack(MAGIC, FORMAT_VERSION, COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W,
+                      h.latent_channels, h.hyper_channels, h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y,
+                      h.nsym_z, h.nsym_y, len(lens_z), len(lens_y))
+    return b"".join((head, lens_z.tobytes(), lens_y.tobytes(), payload_z, payload_y))
+
+
+def parse(data, abi, compute_dtype):
+    """(Header, lens_z, lens_y, payload_z, payload_y) of a container made by `pack`; `abi` and
+    `compute_dtype` are the running build's ic_version() and the model's arithmetic, which the
+    stream must match.  Raises ValueError on anything inconsistent; nothing is launched here."""
+    data = bytes(data)
+    if len(data) < _HEAD.size:
+        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({_HEAD.size})")
+    (magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz,
+     ncy) = _HEAD.unpack_from(data, 0)
+    if magic != MAGIC:
+        raise ValueError(f"codec: bad magic {magic!r}")
+    if ver != FORMAT_VERSION:
+        raise ValueError(f"codec: format version {ver}, this build reads {FORMAT_VERSION}")
+    if dt >= len(COMPUTE_DTYPES):
+        raise ValueError(f"codec: unknown arithmetic tag {dt}")
+    if COMPUTE_DTYPES[dt] != compute_dtype:
+        raise ValueError(f"codec: stream coded with COMPUTE_DTYPE {COMPUTE_DTYPES[dt]!r}, the model runs "
+                         f"{compute_dtype!r}")
+    if s_abi != abi:
+        raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
+    h = Header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky)
+    _check_header(h)
+    if nz != h.nsym_z or ny != h.nsym_y:
+        raise ValueError("codec: symbol counts do not match the batch shape")
+    if ncz != num_chunks(nz, R) or ncy != num_chunks(ny, R):
+        raise ValueError("codec: chunk counts do not match the symbol counts")
+    off = _HEAD.size
+    if len(data) < off + 4 * (ncz + ncy):
+        raise ValueError("codec: buffer ends inside the chunk-length tables")
+    lens_z = np.frombuffer(data, dtype="<u4", count=ncz, offset=off)
+    lens_y = np.frombuffer(data, dtype="<u4", count=ncy, offset=off + 4 * ncz)
+    off += 4 * (ncz + ncy)
+    _check_lengths("z", lens_z, nz, R)
+    _check_lengths("y", lens_y, ny, R)
+    bz, by = int(lens_z.sum(dtype=np.uint64)), int(lens_y.sum(dtype=np.uint64))
+    if off + bz + by != len(data):
+        raise ValueError(f"codec: chunk lengths add up to {bz + by} payload bytes, the buffer holds {len(data) - off}")
+    return h, lens_z, lens_y, data[off:off + bz], data[off + bz:]
+
+
+def split_packed(packed, nsym, R):
+    """(lengths, payload bytes) of the device coder's output buffer [lengths][payload][padding]."""
+    packed = np.asarray(packed, dtype=np.uint8)
+    nc = num_chunks(nsym, R)
+    lens = packed[:4 * nc].view("<u4").copy()
+    total = int(lens.sum(dtype=np.uint64))
+    if 4 * nc + total > packed.size:
+        raise RuntimeError("codec: the coder reported more bytes than its buffer holds")
+    return lens, packed[4 * nc:4 * nc + total].tobytes()
+
+
+def join_packed(lens, payload):
+    """The device decoder's input buffer [lengths][payload] as a uint8 array."""
+    return np.frombuffer(np.ascontiguousarray(lens, dtype="<u4").tobytes() + bytes(payload), dtype=np.uint8)

@@ -1,0 +1,394 @@
+// Entropy coder: wave64-interleaved rANS over quantized CDF tables (ic_codec_*).
+//
+// The bitstream format (lane / word order, chunking, flush) is specified in
+// image_compression_amd/codec.py; the table rule in DESIGN.md.  In short:
+//   * symbols are int32 k in [-K, K]; a table row holds 2K+2 cumulative counts
+//     cdf[0] = 0 < cdf[1] < ... < cdf[2K+1] = 65536 (precision 16);
+//   * a chunk is 64*R consecutive symbols coded by one wavefront: symbol i of the
+//     chunk belongs to lane i % 64, step i / 64; each lane is one rANS coder with a
+//     32-bit state in [2^16, 2^32) and 16-bit renormalisation words;
+//   * chunk bytes = 64 final encoder states (u32, lane order) followed by the
+//     words in the order the decoder takes them: ascending step, ascending lane.
+// The decoder never reads outside its chunk's [begin, end) nor outside a table
+// row, whatever the payload holds: wrong input gives wrong symbols only.
+#include <algorithm>
+
+#include "common.h"
+#include "../../include/imgcomp.h"
+
+namespace {
+
+constexpr int CODEC_KMAX = IC_CODEC_KMAX;            // 2K+1 <= 4095 counts of >= 1 fit 16 bits
+constexpr uint32_t RANS_L = 1u << 16;                // lower bound of the state interval
+constexpr size_t CODEC_LDS_BYTES = 49152;            // tables up to this size are staged in LDS
+
+// ------------------------------------------------------------------ symbolize
+// q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and max|q| by one
+// integer atomic per block (integer max is order-independent: deterministic).
+__global__ void codec_symbolize_k(const float* __restrict__ x, long long n, int* __restrict__ sym,
+                                  int* __restrict__ kmax) {
+  __shared__ int smax[16];
+  int m = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    // |q| beyond 2^30 (or NaN) only has to be reported as too large, not represented
+    const float q = fminf(fmaxf(rintf(x[i]), -1073741824.f), 1073741824.f);
+    const int k = (q == q) ? (int)q : 1073741824;
+    sym[i] = k;
+    m = max(m, k < 0 ? -k : k);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
+  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = max(m, smax[w]);
+    atomicMax(kmax, m);
+  }
+}
+
+// ------------------------------------------------------------------ scale index
+struct ScaleMids {
+  float v[IC_CODEC_MAXL - 1];
+};
+
+// row = number of midpoints strictly below sigma (NaN compares false: row 0)
+__global__ void codec_scale_index_k(const float* __restrict__ sigma, long long n, ScaleMids mids, int nm,
+                                    unsigned char* __restrict__ rows) {
+  __shared__ float sm[IC_CODEC_MAXL - 1];
+  for (int j = threadIdx.x; j < nm; j += blockDim.x) sm[j] = mids.v[j];
+  __syncthreads();
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float s = sigma[i];
+    int r = 0;
+    for (int j = 0; j < nm; ++j) r += s > sm[j] ? 1 : 0;
+    rows[i] = (unsigned char)r;
+  }
+}
+
+// ------------------------------------------------------------------ pmf -> quantized CDF
+// One block per row (DESIGN.md "table rule"): p_j = pmf_j where finite and > 0, else 0; S = sum p_j
+// (fp64, fixed order; S = 0 -> uniform); c_j = 1 + floor(p_j / S * (65536 - M)); the difference
+// 65536 - sum c_j goes to the largest count (lowest index on a tie); cdf = exclusive prefix sum.
+constexpr int TBL_THREADS = 256;
+__global__ void codec_tables_k(const float* __restrict__ pmf, int M, uint32_t* __restrict__ cdf) {
+  __shared__ uint32_t cnt[2 * CODEC_KMAX + 2];
+  __shared__ double part[TBL_THREADS];
+  __shared__ int isum;
+  const float* p = pmf + (size_t)blockIdx.x * M;
+  uint32_t* out = cdf + (size_t)blockIdx.x * (M + 1);
+  const int t = threadIdx.x;
+  double s = 0.0;
+  for (int j = t; j < M; j += TBL_THREADS) {
+    const float v = p[j];
+    s += (v > 0.f && v <= 3.0e38f) ? (double)v : 0.0;
+  }
+  part[t] = s;
+  if (t == 0) isum = 0;
+  __syncthreads();
+  for (int o = TBL_THREADS / 2; o > 0; o >>= 1) {  // fixed tree: deterministic
+    if (t < o) part[t] += part[t + o];
+    __syncthreads();
+  }
+  const double S = part[0];
+  const double budget = (double)(65536 - M);
+  int local = 0;
+  for (int j = t; j < M; j += TBL_THREADS) {
+    const float v = p[j];
+    const double pv = S > 0.0 ? ((v > 0.f && v <= 3.0e38f) ? (double)v / S : 0.0) : 1.0 / (double)M;
+    double f = floor(pv * budget);
+    f = f < 0.0 ? 0.0 : (f > budget ? budget : f);
+    const int c = 1 + (int)f;
+    cnt[j] = (uint32_t)c;
+    local += c;
+  }
+  atomicAdd(&isum, local);  // integer sum: order-independent
+  __syncthreads();
+  if (t == 0) {
+    int d = 65536 - isum;
+    while (d != 0) {  // one pass unless the largest count cannot absorb a negative difference
+      int best = 0;
+      for (int j = 1; j < M; ++j)
+        if (cnt[j] > cnt[best]) best = j;
+      int take = d;
+      if (take < 0 && (int)cnt[best] + take < 1) take = 1 - (int)cnt[best];
+      if (take == 0) break;  // every count is 1 and the total still too large: impossible for M <= 4095
+      cnt[best] = (uint32_t)((int)cnt[best] + take);
+      d -= take;
+    }
+    uint32_t run = 0;
+    for (int j = 0; j < M; ++j) {
+      const uint32_t c = cnt[j];
+      cnt[j] = run;
+      run += c;
+    }
+    cnt[M] = run;
+  }
+  __syncthreads();
+  for (int j = t; j <= M; j += TBL_THREADS) out[j] = cnt[j];
+}
+
+// ------------------------------------------------------------------ rANS
+struct CodecArgs {
+  long long n;                 // symbols of the tensor
+  const unsigned char* rows;   // per-symbol table row, or null: row = global index % C
+  int C;
+  const uint32_t* cdf;         // [nrows][M + 1]
+  int nrows, K, R;
+};
+
+// the tables in LDS (LDS = true) or where they are
+template <bool LDS>
+__device__ __forceinline__ const uint32_t* stage_tables(const CodecArgs& a, uint32_t* lds) {
+  if (!LDS) return a.cdf;
+  const int words = a.nrows * (2 * a.K + 2);
+  for (int j = threadIdx.x; j < words; j += 64) lds[j] = a.cdf[j];
+  __syncthreads();
+  return lds;
+}
+
+__device__ __forceinline__ int row_of(const CodecArgs& a, long long g) {
+  const int r = a.rows ? (int)a.rows[g] : (int)(g % a.C);
+  return min(r, a.nrows - 1);
+}
+
+// One wavefront per chunk.  Steps run last to first; at a step the lanes whose state would leave
+// [2^16, 2^32) each emit their low 16 bits first.  Words are laid down from the slot's end towards its
+// start, a step's emitters in ascending lane order, so that read forward they come in ascending step,
+// ascending lane; the 64 final states go in front.  slot = 2*64*R + 256 bytes is the worst case (one
+// word per symbol).  lengths[chunk] = bytes used; they end at the slot's end.
+template <bool LDS>
+__global__ void __launch_bounds__(64) codec_encode_k(const int* __restrict__ sym, CodecArgs a,
+                                                     unsigned short* __restrict__ scratch,
+                                                     uint32_t* __restrict__ lengths) {
+  extern __shared__ uint32_t lds[];
+  const uint32_t* tab = stage_tables<LDS>(a, lds);
+  const int lane = threadIdx.x;
+  const int M1 = 2 * a.K + 2;
+  const long long per = 64ll * a.R;
+  const long long c0 = (long long)blockIdx.x * per;
+  const int nc = (int)min(per, a.n - c0);
+  const int steps = (nc + 63) >> 6;
+  const size_t slot_words = (size_t)per + 128;
+  unsigned short* slot = scratch + (size_t)blockIdx.x * slot_words;
+  long long ptr = (long long)slot_words;
+  uint32_t x = RANS_L;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (int t = steps - 1; t >= 0; --t) {
+    const int i = t * 64 + lane;
+    const bool active = i < nc;
+    uint32_t start = 0, freq = 1;
+    if (active) {
+      const long long g = c0 + i;
+      const int j = min(max(sym[g] + a.K, 0), 2 * a.K);
+      const uint32_t* row = tab + (size_t)row_of(a, g) * M1;
+      start = row[j];
+      freq = row[j + 1] - start;
+    }
+    const bool emit = active && (unsigned long long)x >= ((unsigned long long)freq << 16);
+    const unsigned long long mask = __ballot(emit);
+    const int cnt = __popcll(mask);
+    if (emit) {
+      slot[ptr - cnt + __popcll(mask & below)] = (unsigned short)(x & 0xffffu);
+      x >>= 16;
+    }
+    ptr -= cnt;
+    if (active) x = ((x / freq) << 16) + (x % freq) + start;
+  }
+  ptr -= 128;
+  slot[ptr + 2 * lane] = (unsigned short)(x & 0xffffu);
+  slot[ptr + 2 * lane + 1] = (unsigned short)(x >> 16);
+  if (lane == 0) lengths[blockIdx.x] = (uint32_t)((slot_words - (size_t)ptr) * 2);
+}
+
+// out = [lengths: nchunks x u32][chunk 0 bytes][chunk 1 bytes]...; block = chunk; its offset is the
+// exclusive scan of the lengths, summed by the block itself (integer: any order)
+__global__ void codec_compact_k(const unsigned short* __restrict__ scratch, const uint32_t* __restrict__ lengths,
+                                int nchunks, int R, unsigned short* __restrict__ out) {
+  __shared__ unsigned long long part[256];
+  unsigned long long s = 0;
+  for (int c = threadIdx.x; c < (int)blockIdx.x; c += blockDim.x) s += lengths[c];
+  part[threadIdx.x] = s;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) part[threadIdx.x] += part[threadIdx.x + o];
+    __syncthreads();
+  }
+  const size_t slot_words = 64ull * R + 128;
+  const size_t len_w = min((size_t)lengths[blockIdx.x] / 2, slot_words);
+  const unsigned short* src = scratch + (size_t)blockIdx.x * slot_words + (slot_words - len_w);
+  unsigned short* dst = out + 2 * (size_t)nchunks + part[0] / 2;
+  for (size_t k = threadIdx.x; k < len_w; k += blockDim.x) dst[k] = src[k];
+  if (threadIdx.x < 2) {  // the length itself, as two little-endian halves
+    const uint32_t L = lengths[blockIdx.x];
+    out[2 * (size_t)blockIdx.x + threadIdx.x] = (unsigned short)(threadIdx.x ? (L >> 16) : (L & 0xffffu));
+  }
+}
+
+// The mirror of codec_encode_k.  in = the compact buffer ([lengths][payload], in_words 16-bit words in
+// all).  Every read of `in` is guarded by the chunk's [begin, end), itself clamped to the buffer; the
+// search stays inside the symbol's row.
+template <bool LDS>
+__global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __restrict__ in, size_t in_words,
+                                                     int nchunks, CodecArgs a, float* __restrict__ out) {
+  extern __shared__ uint32_t lds[];
+  __shared__ unsigned long long part[64];
+  const uint32_t* tab = stage_tables<LDS>(a, lds);
+  const int lane = threadIdx.x;
+  const uint32_t* lens = reinterpret_cast<const uint32_t*>(in);  // 2 * nchunks <= in_words (checked by the host)
+  unsigned long long s = 0;
+  for (int c = lane; c < (int)blockIdx.x; c += 64) s += lens[c];
+  part[lane] = s;
+  __syncthreads();
+  if (lane == 0) {
+    unsigned long long tot = 0;
+    for (int l = 0; l < 64; ++l) tot += part[l];
+    part[0] = tot;
+  }
+  __syncthreads();
+  const size_t begin = min((size_t)(2ull * nchunks + part[0] / 2), in_words);
+  const size_t end = min(begin + (size_t)lens[blockIdx.x] / 2, in_words);
+  auto word = [&](size_t w) -> uint32_t { return w < end ? (uint32_t)in[w] : 0u; };
+
+  const int M = 2 * a.K + 1, M1 = M + 1;
+  int iters = 0;
+  while ((1 << iters) < M) ++iters;
+  const long long per = 64ll * a.R;
+  const long long c0 = (long long)blockIdx.x * per;
+  const int nc = (int)min(per, a.n - c0);
+  const int steps = (nc + 63) >> 6;
+  uint32_t x = word(begin + 2 * lane) | (word(begin + 2 * lane + 1) << 16);
+  size_t cur = begin + 128;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (int t = 0; t < steps; ++t) {
+    const int i = t * 64 + lane;
+    const bool active = i < nc;
+    bool refill = false;
+    if (active) {
+      const long long g = c0 + i;
+      const uint32_t* row = tab + (size_t)row_of(a, g) * M1;
+      const uint32_t slot = x & 0xffffu;
+      int lo = 0, hi = M - 1;  // largest j in [0, M-1] with row[j] <= slot (row[0] = 0)
+      for (int it = 0; it < iters; ++it) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (row[mid] <= slot) lo = mid; else hi = mid - 1;
+      }
+      const uint32_t start = row[lo], freq = row[lo + 1] - start;
+      x = freq * (x >> 16) + slot - start;
+      refill = x < RANS_L;
+      out[g] = (float)(lo - a.K);
+    }
+    const unsigned long long mask = __ballot(refill);
+    if (refill) x = (x << 16) | word(cur + __popcll(mask & below));
+    cur += __popcll(mask);
+  }
+}
+
+bool codec_args_ok(long long n, const void* rows, int C, int nrows, int K, int R) {
+  if (n < 1 || nrows < 1 || K < 0 || K > CODEC_KMAX || R < 1 || R > IC_CODEC_MAXR) return false;
+  if (!rows && (C < 1 || C > nrows)) return false;
+  return (n + 64ll * R - 1) / (64ll * R) <= 0x7fffffffll;
+}
+
+size_t table_bytes(int nrows, int K) { return (size_t)nrows * (2 * K + 2) * sizeof(uint32_t); }
+
+}  // namespace
+
+extern "C" {
+
+int ic_codec_symbolize(const float* x, long long n, int* sym, int* kmax_dev, int* kmax_host, void* stream) {
+  if (!x || !sym || !kmax_dev || !kmax_host || n < 1) return IC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(kmax_dev, 0, sizeof(int), st);
+  if (e != hipSuccess) return (int)e;
+  const int blocks = (int)std::min<long long>((n + 255) / 256, 1024);
+  hipLaunchKernelGGL(codec_symbolize_k, dim3(blocks), dim3(256), 0, st, x, n, sym, kmax_dev);
+  IC_CHECK_LAUNCH();
+  e = hipMemcpyAsync(kmax_host, kmax_dev, sizeof(int), hipMemcpyDeviceToHost, st);
+  if (e != hipSuccess) return (int)e;
+  e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  return *kmax_host > CODEC_KMAX ? IC_ERR_ARG : IC_OK;
+}
+
+int ic_codec_scale_index(const float* sigma, long long n, const float* mids, int L, unsigned char* rows,
+                         void* stream) {
+  if (!sigma || !rows || n < 1 || L < 1 || L > IC_CODEC_MAXL || (L > 1 && !mids)) return IC_ERR_ARG;
+  ScaleMids m;
+  for (int j = 0; j < IC_CODEC_MAXL - 1; ++j) m.v[j] = j < L - 1 ? mids[j] : 0.f;
+  for (int j = 1; j < L - 1; ++j)
+    if (!(m.v[j] >= m.v[j - 1])) return IC_ERR_ARG;  // the count of midpoints below sigma needs them sorted
+  const int blocks = (int)std::min<long long>((n + 255) / 256, 2048);
+  hipLaunchKernelGGL(codec_scale_index_k, dim3(blocks), dim3(256), 0, (hipStream_t)stream, sigma, n, m, L - 1, rows);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_build_tables(const float* pmf, int rows, int K, unsigned int* cdf, void* stream) {
+  if (!pmf || !cdf || rows < 1 || K < 0 || K > CODEC_KMAX) return IC_ERR_ARG;
+  hipLaunchKernelGGL(codec_tables_k, dim3(rows), dim3(TBL_THREADS), 0, (hipStream_t)stream, pmf, 2 * K + 1, cdf);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+long long ic_codec_chunks(long long n, int steps_per_chunk) {
+  if (n < 1 || steps_per_chunk < 1 || steps_per_chunk > IC_CODEC_MAXR) return 0;
+  return (n + 64ll * steps_per_chunk - 1) / (64ll * steps_per_chunk);
+}
+
+size_t ic_codec_encode_ws(long long n, int steps_per_chunk) {
+  const long long c = ic_codec_chunks(n, steps_per_chunk);
+  return c < 1 ? 0 : (size_t)c * (128ull * steps_per_chunk + 256);
+}
+
+size_t ic_codec_compact_bytes(long long n, int steps_per_chunk) {
+  const long long c = ic_codec_chunks(n, steps_per_chunk);
+  return c < 1 ? 0 : (size_t)c * 4 + ic_codec_encode_ws(n, steps_per_chunk);
+}
+
+int ic_codec_encode(const int* sym, long long n, const unsigned char* rows, int C, const unsigned int* cdf,
+                    int nrows, int K, int steps_per_chunk, void* ws, size_t ws_bytes, unsigned int* lengths,
+                    void* stream) {
+  if (!sym || !cdf || !ws || !lengths || !codec_args_ok(n, rows, C, nrows, K, steps_per_chunk)) return IC_ERR_ARG;
+  if (ws_bytes < ic_codec_encode_ws(n, steps_per_chunk)) return IC_ERR_WORKSPACE;
+  const CodecArgs a{n, rows, C, cdf, nrows, K, steps_per_chunk};
+  const int chunks = (int)ic_codec_chunks(n, steps_per_chunk);
+  const size_t tb = table_bytes(nrows, K);
+  if (tb <= CODEC_LDS_BYTES)
+    hipLaunchKernelGGL(codec_encode_k<true>, dim3(chunks), dim3(64), tb, (hipStream_t)stream, sym, a,
+                       (unsigned short*)ws, lengths);
+  else
+    hipLaunchKernelGGL(codec_encode_k<false>, dim3(chunks), dim3(64), 0, (hipStream_t)stream, sym, a,
+                       (unsigned short*)ws, lengths);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_compact(const void* ws, const unsigned int* lengths, long long n, int steps_per_chunk, void* out,
+                     size_t out_bytes, void* stream) {
+  const long long chunks = ic_codec_chunks(n, steps_per_chunk);
+  if (!ws || !lengths || !out || chunks < 1 || chunks > 0x7fffffffll) return IC_ERR_ARG;
+  if (out_bytes < ic_codec_compact_bytes(n, steps_per_chunk)) return IC_ERR_WORKSPACE;
+  hipLaunchKernelGGL(codec_compact_k, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)ws, lengths, (int)chunks, steps_per_chunk, (unsigned short*)out);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_decode(const void* in, size_t in_bytes, long long n, const unsigned char* rows, int C,
+                    const unsigned int* cdf, int nrows, int K, int steps_per_chunk, float* out, void* stream) {
+  if (!in || !cdf || !out || !codec_args_ok(n, rows, C, nrows, K, steps_per_chunk)) return IC_ERR_ARG;
+  const int chunks = (int)ic_codec_chunks(n, steps_per_chunk);
+  if (in_bytes < 4ull * chunks) return IC_ERR_ARG;  // the length table itself must be inside the buffer
+  const CodecArgs a{n, rows, C, cdf, nrows, K, steps_per_chunk};
+  const size_t tb = table_bytes(nrows, K);
+  if (tb <= CODEC_LDS_BYTES)
+    hipLaunchKernelGGL(codec_decode_k<true>, dim3(chunks), dim3(64), tb, (hipStream_t)stream,
+                       (const unsigned short*)in, in_bytes / 2, chunks, a, out);
+  else
+    hipLaunchKernelGGL(codec_decode_k<false>, dim3(chunks), dim3(64), 0, (hipStream_t)stream,
+                       (const unsigned short*)in, in_bytes / 2, chunks, a, out);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+}  // extern "C"

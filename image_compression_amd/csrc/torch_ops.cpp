@@ -1118,6 +1118,127 @@ std::tuple<Tensor, Tensor> msssim_bwd_meta(const Tensor& g, const Tensor&, at::I
           need_b ? at::empty(shape, g.options()) : at::empty({0}, g.options())};
 }
 
+// ---------------------------------------------------------------- entropy coder (imgcomp_codec)
+// compress / decompress only (never the training step): symbols int32, table rows uint8, tables int32
+// [rows][2K+2] (the C ABI's uint32 counts, all <= 65536), byte buffers uint8.
+void check_codec(const Tensor& t, at::ScalarType ty, const char* what) {
+  TORCH_CHECK(t.is_cuda(), "imgcomp_codec: ", what, " must be on a ROCm device, got ", t.device());
+  TORCH_CHECK(t.scalar_type() == ty && t.is_contiguous(), "imgcomp_codec: ", what, " must be contiguous ", ty);
+}
+
+int64_t codec_k(const Tensor& cdf) {
+  TORCH_CHECK(cdf.dim() == 2 && cdf.size(1) >= 2 && cdf.size(1) % 2 == 0 && cdf.size(1) <= 2 * IC_CODEC_KMAX + 2,
+              "imgcomp_codec: tables must be [rows][2K+2] with K <= ", IC_CODEC_KMAX, ", got ", cdf.sizes());
+  return cdf.size(1) / 2 - 1;
+}
+
+const unsigned char* codec_rows(const std::optional<Tensor>& rows, int64_t n) {
+  if (!rows.has_value() || !rows->defined()) return nullptr;
+  check_codec(*rows, at::kByte, "rows");
+  TORCH_CHECK(rows->numel() == n, "imgcomp_codec: one table row per symbol");
+  return rows->data_ptr<unsigned char>();
+}
+
+std::tuple<Tensor, int64_t> codec_symbolize(const Tensor& x) {
+  check_dense(x, "x");
+  TORCH_CHECK(x.numel() > 0, "imgcomp_codec: empty tensor");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor sym = at::empty({x.numel()}, x.options().dtype(at::kInt));
+  Tensor kd = at::empty({1}, x.options().dtype(at::kInt));
+  int kmax = 0;
+  const int rc = ic_codec_symbolize(x.data_ptr<float>(), x.numel(), sym.data_ptr<int>(), kd.data_ptr<int>(), &kmax,
+                                    stream_of(x));
+  TORCH_CHECK_VALUE(!(rc == IC_ERR_ARG && kmax > IC_CODEC_KMAX), "imgcomp_codec: a symbol of magnitude ", kmax,
+                    " exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "codec_symbolize");
+  return {sym, (int64_t)kmax};
+}
+
+Tensor codec_scale_index(const Tensor& sigma, at::ArrayRef<double> mids) {
+  check_dense(sigma, "sigma");
+  TORCH_CHECK(sigma.numel() > 0 && (int64_t)mids.size() < IC_CODEC_MAXL, "imgcomp_codec: at most ", IC_CODEC_MAXL,
+              " scales");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sigma.device());
+  std::vector<float> m(mids.begin(), mids.end());
+  Tensor rows = at::empty({sigma.numel()}, sigma.options().dtype(at::kByte));
+  check_rc(ic_codec_scale_index(sigma.data_ptr<float>(), sigma.numel(), m.data(), (int)m.size() + 1,
+                                rows.data_ptr<unsigned char>(), stream_of(sigma)),
+           "codec_scale_index");
+  return rows;
+}
+
+Tensor codec_build_tables(const Tensor& pmf) {
+  check_operand(pmf, "pmf");
+  TORCH_CHECK(pmf.dim() == 2 && pmf.is_contiguous() && pmf.size(0) >= 1 && pmf.size(1) % 2 == 1 &&
+                  pmf.size(1) <= 2 * IC_CODEC_KMAX + 1,
+              "imgcomp_codec: pmf must be contiguous [rows][2K+1] with K <= ", IC_CODEC_KMAX, ", got ", pmf.sizes());
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(pmf.device());
+  Tensor cdf = at::empty({pmf.size(0), pmf.size(1) + 1}, pmf.options().dtype(at::kInt));
+  check_rc(ic_codec_build_tables(pmf.data_ptr<float>(), (int)pmf.size(0), (int)(pmf.size(1) / 2),
+                                 (unsigned int*)cdf.data_ptr<int>(), stream_of(pmf)),
+           "codec_build_tables");
+  return cdf;
+}
+
+// [lengths: chunks x u32][payload], padded to the worst case (the lengths say how much is payload)
+Tensor codec_encode(const Tensor& sym, const std::optional<Tensor>& rows, int64_t C, const Tensor& cdf, int64_t steps) {
+  check_codec(sym, at::kInt, "sym");
+  check_codec(cdf, at::kInt, "tables");
+  const int64_t K = codec_k(cdf), n = sym.numel();
+  const unsigned char* rp = codec_rows(rows, n);
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR && n > 0, "imgcomp_codec: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  const size_t nb = ic_codec_encode_ws(n, (int)steps), ob = ic_codec_compact_bytes(n, (int)steps);
+  Tensor ws = at::empty({(int64_t)nb}, sym.options().dtype(at::kByte));
+  Tensor lens = at::empty({(int64_t)ic_codec_chunks(n, (int)steps)}, sym.options().dtype(at::kInt));
+  Tensor out = at::empty({(int64_t)ob}, sym.options().dtype(at::kByte));
+  check_rc(ic_codec_encode(sym.data_ptr<int>(), n, rp, (int)C, (const unsigned int*)cdf.data_ptr<int>(),
+                           (int)cdf.size(0), (int)K, (int)steps, ws.data_ptr(), nb, (unsigned int*)lens.data_ptr<int>(),
+                           stream_of(sym)),
+           "codec_encode");
+  check_rc(ic_codec_compact(ws.data_ptr(), (const unsigned int*)lens.data_ptr<int>(), n, (int)steps, out.data_ptr(), ob,
+                            stream_of(sym)),
+           "codec_compact");
+  return out;
+}
+
+Tensor codec_decode(const Tensor& packed, int64_t n, const std::optional<Tensor>& rows, int64_t C, const Tensor& cdf,
+                    int64_t steps) {
+  check_codec(packed, at::kByte, "packed");
+  check_codec(cdf, at::kInt, "tables");
+  const int64_t K = codec_k(cdf);
+  TORCH_CHECK(n > 0, "imgcomp_codec: no symbols");
+  const unsigned char* rp = codec_rows(rows, n);
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR, "imgcomp_codec: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  TORCH_CHECK(((uintptr_t)packed.data_ptr() & 3) == 0, "imgcomp_codec: packed buffer must be 4-byte aligned");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(packed.device());
+  Tensor out = at::empty({n}, packed.options().dtype(at::kFloat));
+  check_rc(ic_codec_decode(packed.data_ptr(), (size_t)packed.numel(), n, rp, (int)C,
+                           (const unsigned int*)cdf.data_ptr<int>(), (int)cdf.size(0), (int)K, (int)steps,
+                           out.data_ptr<float>(), stream_of(packed)),
+           "codec_decode");
+  return out;
+}
+
+std::tuple<Tensor, int64_t> codec_symbolize_meta(const Tensor& x) {
+  return {at::empty({x.numel()}, x.options().dtype(at::kInt)), 0};
+}
+Tensor codec_scale_index_meta(const Tensor& sigma, at::ArrayRef<double>) {
+  return at::empty({sigma.numel()}, sigma.options().dtype(at::kByte));
+}
+Tensor codec_build_tables_meta(const Tensor& pmf) {
+  TORCH_CHECK(pmf.dim() == 2, "imgcomp_codec: pmf must be [rows][2K+1]");
+  return at::empty({pmf.size(0), pmf.size(1) + 1}, pmf.options().dtype(at::kInt));
+}
+Tensor codec_encode_meta(const Tensor& sym, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t steps) {
+  const size_t ob = ic_codec_compact_bytes(sym.numel(), (int)steps);
+  TORCH_CHECK(ob > 0, "imgcomp_codec: bad symbol count or steps_per_chunk");
+  return at::empty({(int64_t)ob}, sym.options().dtype(at::kByte));
+}
+Tensor codec_decode_meta(const Tensor& packed, int64_t n, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t) {
+  return at::empty({n}, packed.options().dtype(at::kFloat));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1295,4 +1416,29 @@ TORCH_LIBRARY_IMPL(imgcomp, Meta, m) {
   m.impl("philox_advance", philox_advance_meta);
   m.impl("msssim_fwd", msssim_fwd_meta);
   m.impl("msssim_bwd", msssim_bwd_meta);
+}
+
+// The entropy coder's ops live in a namespace of their own: imgcomp holds exactly the training step's launchers.
+TORCH_LIBRARY(imgcomp_codec, m) {
+  m.def("symbolize(Tensor x) -> (Tensor, int)");
+  m.def("scale_index(Tensor sigma, float[] mids) -> Tensor");
+  m.def("build_tables(Tensor pmf) -> Tensor");
+  m.def("encode(Tensor sym, Tensor? rows, int channels, Tensor tables, int steps_per_chunk) -> Tensor");
+  m.def("decode(Tensor packed, int n, Tensor? rows, int channels, Tensor tables, int steps_per_chunk) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_codec, CUDA, m) {
+  m.impl("symbolize", codec_symbolize);
+  m.impl("scale_index", codec_scale_index);
+  m.impl("build_tables", codec_build_tables);
+  m.impl("encode", codec_encode);
+  m.impl("decode", codec_decode);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_codec, Meta, m) {
+  m.impl("symbolize", codec_symbolize_meta);
+  m.impl("scale_index", codec_scale_index_meta);
+  m.impl("build_tables", codec_build_tables_meta);
+  m.impl("encode", codec_encode_meta);
+  m.impl("decode", codec_decode_meta);
 }

@@ -12,7 +12,9 @@ Kodak evaluator and its metrics, on HIP kernels.
 * `Evaluator.run_eval(batches)` — engine/evaluator.py:67-105: eval mode,
   no_grad, forward, drop total_loss, update metrics and losses; returns the
   mean results dict {psnr, ms_ssim, bpp, y_entropy, z_entropy, <distortion>};
-  `graph=True` replays a hipGraph-captured forward per input shape (`GraphForward`).
+  `graph=True` replays a hipGraph-captured forward per input shape (`GraphForward`);
+  `coded=True` also entropy-codes every batch (`model.compress`) and adds `coded_bpp`, the
+  bits of the real bitstream per pixel, beside the estimated `bpp`.
 """
 import contextlib
 import ctypes
@@ -162,12 +164,17 @@ class Evaluator:
     """engine/evaluator.py:44-123 without the data loader / file outputs:
     run_eval(batches) over an iterable of [N,3,H,W] images in [0,1].  graph=True replays one
     captured forward per input shape (GraphForward) instead of launching it eagerly;
-    weight_cache=False re-packs the weights on every eager forward (functional.weight_cache)."""
+    weight_cache=False re-packs the weights on every eager forward (functional.weight_cache).
+    coded=True (eager path only) also compresses each batch and reports
+    coded_bpp = 8 * len(bytes) / (N * H * W), averaged like the losses."""
 
-    def __init__(self, model, device=None, graph=False, weight_cache=True):
+    def __init__(self, model, device=None, graph=False, weight_cache=True, coded=False):
+        if coded and graph:
+            raise ValueError("Evaluator: coded=True runs on the eager path only (graph=False)")
         self.model = model
         self.device = device
-        self.monitor = Monitor(model.loss_names)
+        self.coded = bool(coded)
+        self.monitor = Monitor(list(model.loss_names) + (["coded_bpp"] if self.coded else []))
         self.graph = graph
         self.weight_cache = weight_cache
         self._graphs = {}
@@ -205,6 +212,9 @@ class Evaluator:
                         imgs = imgs.to(self.device, non_blocking=True)
                     x_tilde, losses = self._forward(imgs)
                     losses.pop("total_loss")
+                    if self.coded:
+                        data = self.model.compress(imgs)
+                        losses["coded_bpp"] = 8.0 * len(data) / (imgs.shape[0] * imgs.shape[2] * imgs.shape[3])
                     self.monitor.update_metric(x_tilde, imgs)
                     self.monitor.update_loss(**losses)
         finally:

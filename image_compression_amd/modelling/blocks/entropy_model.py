@@ -16,8 +16,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import _lib
+from ... import codec as _codec
 from ... import noise as _noise
-from ...functional import CELossFn, conditional, conditional_likelihood, factorized, quantize
+from ...functional import CELossFn, _to_last, conditional, conditional_likelihood, factorized, quantize
 from .build import ENTROPY_MODEL_REGISTRY
 
 LOG2 = math.log(2.0)
@@ -90,9 +92,40 @@ class BaseEntropyModel(nn.Module):
     def decompress(self, x):
         raise NotImplementedError()
 
+    def _codable(self):
+        if self.training:
+            raise RuntimeError("compress / decompress run in eval mode only (rounding, not noise)")
+        if float(self.bin) != 1.0:
+            raise NotImplementedError(f"the entropy coder codes integer symbols: BIN must be 1, got {self.bin}")
+
     def _ce_loss(self, probs):
         """sum clamp(-log2(p + 1e-10), 0, 50) — deterministic HIP reduction."""
         return CELossFn.apply(probs)
+
+
+def symbolize(x):
+    """x (N, C, *) -> (int32 symbols flattened in (n, *, c) order, kmax = max |symbol|): the
+    eval-mode rounding of `quantize` / `factorized`.  ValueError beyond the coder's limit."""
+    _lib.require_device(x)
+    sym, kmax = _lib.codec_ops().symbolize(_to_last(x))
+    return sym, int(kmax)
+
+
+def symbols_as_tensor(flat, shape):
+    """Float symbols flattened in (n, *, c) order -> the logical (N, C, *) tensor over that
+    channels-last storage: the layout the eval forward's quantized tensors have."""
+    return flat.view(shape[0], *shape[2:], shape[1]).movedim(-1, 1)
+
+
+def _encode(sym, rows, channels, tables, steps):
+    packed = _lib.codec_ops().encode(sym, rows, int(channels), tables, int(steps))
+    lens, payload = _codec.split_packed(packed.cpu().numpy(), sym.numel(), steps)  # the one D2H copy
+    return payload, lens
+
+
+def _decode(payload, lengths, n, rows, channels, tables, steps, device):
+    buf = torch.from_numpy(_codec.join_packed(lengths, payload).copy()).to(device)
+    return _lib.codec_ops().decode(buf, int(n), rows, int(channels), tables, int(steps))
 
 
 def _ref_layout(p):
@@ -121,14 +154,90 @@ class EntropyModel(BaseEntropyModel):
     def _logit_cumulative(self, x):
         return self._cdf_estimator(x)
 
+    # ---- entropy coding (eval only): one table row per channel, rebuilt per call from the weights
+    @property
+    def channels(self):
+        return self._cdf_estimator.layers[0].weight.shape[1]
+
+    def tables(self, kmax):
+        """Quantized CDFs [C][2K+2] of the integers -K..K under the current weights: the eval-mode
+        likelihood kernel on the grid (1, C, 2K+1, 1), then the table kernel."""
+        self._codable()
+        dev = self._cdf_estimator.layers[0].weight.device
+        K = int(kmax)
+        grid = torch.arange(-K, K + 1, device=dev, dtype=torch.float32).view(1, 1, -1, 1).expand(1, self.channels, -1, 1)
+        with torch.no_grad():
+            _, p = factorized(grid, self._cdf_estimator.flat_params(), False, None, self._cdf_estimator.dims, self.bin)
+            return _lib.codec_ops().build_tables(p[0, :, :, 0].contiguous())
+
+    def encode_symbols(self, sym, kmax, steps_per_chunk=1024):
+        return _encode(sym, None, self.channels, self.tables(kmax), steps_per_chunk)
+
+    @torch.no_grad()
+    def compress(self, z, steps_per_chunk=1024):
+        """z (N, C, *) -> (payload bytes, chunk lengths uint32[chunks], kmax)."""
+        self._codable()
+        sym, kmax = symbolize(z)
+        payload, lens = self.encode_symbols(sym, kmax, steps_per_chunk)
+        return payload, lens, kmax
+
+    @torch.no_grad()
+    def decompress(self, payload, shape, lengths, kmax, steps_per_chunk=1024):
+        """The float tensor of integers (N, C, *) = `shape` that `compress` coded."""
+        self._codable()
+        tables = self.tables(kmax)
+        n = math.prod(shape)
+        flat = _decode(payload, lengths, n, None, self.channels, tables, steps_per_chunk, tables.device)
+        return symbols_as_tensor(flat, tuple(shape))
+
 
 class SymmetricConditionalModel(BaseEntropyModel):
     """entropy_model.py:272-352; subclasses pick the standardized CDF."""
     KIND = None
 
-    def __init__(self, cfg):
+    def __init__(self, cfg, scale_min=0.11, scale_max=256., num_scales=64):
         super().__init__()
         self.bin = cfg.MODEL.ENTROPY_MODEL.BIN
+        # the entropy coder's scale table: num_scales log-spaced scales (compress / decompress only)
+        self.scale_min, self.scale_max, self.num_scales = float(scale_min), float(scale_max), int(num_scales)
+
+    # ---- entropy coding (eval only): one table row per table scale, rebuilt per call
+    def tables(self, kmax, device):
+        """Quantized CDFs [L][2K+2] of the integers -K..K at each table scale: the likelihood
+        kernel (mode 4) on the grid, then the table kernel."""
+        self._codable()
+        K = int(kmax)
+        scales, _ = _codec.scale_table(self.num_scales, self.scale_min, self.scale_max)
+        grid = torch.arange(-K, K + 1, device=device, dtype=torch.float32).expand(self.num_scales, -1).contiguous()
+        scale = torch.from_numpy(scales).to(device).view(-1, 1).expand_as(grid).contiguous()
+        with torch.no_grad():
+            return _lib.codec_ops().build_tables(conditional_likelihood(grid, scale, None, self.KIND, self.bin))
+
+    def scale_rows(self, sigma):
+        """uint8 table row of every sigma (N, C, *), flattened in (n, *, c) order."""
+        _lib.require_device(sigma)
+        _, mids = _codec.scale_table(self.num_scales, self.scale_min, self.scale_max)
+        return _lib.codec_ops().scale_index(_to_last(sigma), [float(m) for m in mids])
+
+    def encode_symbols(self, sym, kmax, sigma, steps_per_chunk=1024):
+        return _encode(sym, self.scale_rows(sigma), 0, self.tables(kmax, sigma.device), steps_per_chunk)
+
+    @torch.no_grad()
+    def compress(self, y, sigma, steps_per_chunk=1024):
+        """y, sigma (N, C, *) -> (payload bytes, chunk lengths uint32[chunks], kmax)."""
+        self._codable()
+        sym, kmax = symbolize(y)
+        payload, lens = self.encode_symbols(sym, kmax, sigma.expand_as(y), steps_per_chunk)
+        return payload, lens, kmax
+
+    @torch.no_grad()
+    def decompress(self, payload, sigma, lengths, kmax, steps_per_chunk=1024):
+        """The float tensor of integers, shaped like sigma, that `compress` coded with this sigma."""
+        self._codable()
+        tables = self.tables(kmax, sigma.device)
+        flat = _decode(payload, lengths, sigma.numel(), self.scale_rows(sigma), 0, tables, steps_per_chunk,
+                       sigma.device)
+        return symbols_as_tensor(flat, tuple(sigma.shape))
 
     def quantize(self, x):
         """_quantize on its own (train: noise, eval: round): with likelihood() the two halves of

@@ -9,8 +9,11 @@ import os
 import torch
 import torch.nn as nn
 
+from ... import _lib
+from ... import codec as _codec
 from ... import noise as _noise
 from ...functional import AbsFn, NonNegMultiFn, route_weight_gradients
+from ..blocks.entropy_model import symbolize, symbols_as_tensor
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
@@ -199,9 +202,54 @@ class Compressor2018(nn.Module):
     def distortion_loss(self, img1, img2):
         return {name: fn(img1, img2) for name, fn in self.distortion_loss_fns.items()}
 
-    def compress(self, x):
-        """Stub in the reference (bmshl2018.py:106-107): no entropy coder."""
-        return None
+    # ---- real bitstreams (beyond the reference, whose compress / decompress are stubs:
+    # bmshl2018.py:106-110).  Format and contract: image_compression_amd/codec.py, INTEGRATION.md.
+    def _codable(self):
+        if self.training:
+            raise RuntimeError("compress / decompress run in eval mode only: call model.eval() first")
+        self._clear_reparameterised()
 
-    def decompress(self, x):
-        return None
+    @torch.no_grad()
+    def compress(self, x, steps_per_chunk=1024):
+        """x (N, 3, H, W) in [0, 1], H and W multiples of 64 -> one bytes object for the batch."""
+        self._codable()
+        if x.dim() != 4 or x.shape[2] % _codec.Z_DOWN or x.shape[3] % _codec.Z_DOWN:
+            raise ValueError(f"compress: image size {tuple(x.shape)} must be (N, C, H, W) with H and W "
+                             f"multiples of {_codec.Z_DOWN}")
+        em, cm = self.entropy_model, self.conditional_model
+        N, _, H, W = x.shape
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(AbsFn.apply(y))
+        z_sym, kz = symbolize(z)
+        # sigma from the integers the decoder will hold, in the layout it will hold them in
+        sigma = self.prior_synthesis(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
+        pz, lz = em.encode_symbols(z_sym, kz, steps_per_chunk)
+        y_sym, ky = symbolize(y)
+        py, ly = cm.encode_symbols(y_sym, ky, sigma.expand_as(y), steps_per_chunk)
+        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], cm.KIND, getattr(self, "compute_dtype", "fp32"),
+                          int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max, int(steps_per_chunk),
+                          kz, ky)
+        if tuple(z.shape) != h.z_shape or tuple(y.shape) != h.y_shape:
+            raise ValueError(f"compress: latents {tuple(y.shape)} / {tuple(z.shape)} are not the image size over "
+                             f"{_codec.Y_DOWN} / {_codec.Z_DOWN}")
+        return _codec.pack(h, lz, ly, pz, py)
+
+    @torch.no_grad()
+    def decompress(self, data):
+        """bytes from `compress` (same weights, build, COMPUTE_DTYPE, device type and batch shape) ->
+        x_hat (N, 3, H, W), the eval forward's reconstruction."""
+        self._codable()
+        em, cm = self.entropy_model, self.conditional_model
+        h, lz, ly, pz, py = _codec.parse(data, int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32"))
+        if h.kind != cm.KIND or h.hyper_channels != em.channels:
+            raise ValueError("decompress: the stream was coded by a different model (conditional kind / channels)")
+        if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
+            raise ValueError("decompress: the stream was coded with a different scale table")
+        z_hat = em.decompress(pz, h.z_shape, lz, h.kmax_z, h.R)
+        sigma = self.prior_synthesis(z_hat)
+        if tuple(sigma.shape) != h.y_shape:
+            raise ValueError(f"decompress: the model's sigma {tuple(sigma.shape)} is not the stream's latent shape "
+                             f"{h.y_shape}")
+        y_hat = cm.decompress(py, sigma, ly, h.kmax_y, h.R)
+        x_hat = self.synthesis_transform(y_hat)
+        return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)

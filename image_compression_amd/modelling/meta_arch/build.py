@@ -90,4 +90,5 @@ def set_compute_dtype(model, dtype):
                     m.xb |= 2
                 if isinstance(prv, Conv2d) and prv.in_channels == 192 and prv.out_channels % 64 == 0:
                     m.xb |= 2
+    model.compute_dtype = dtype  # recorded for the compressed container's arithmetic tag (codec.py)
     return model

@@ -54,7 +54,7 @@ typedef struct ic_act {
 } ic_act;
 
 /* ---- library ---- */
-int ic_version(void);                 /* ABI version (monotonic; 3: ic_fact_net with IC_FACT_NET_MAXL layers) */
+int ic_version(void);                 /* ABI version (monotonic; 3: ic_fact_net with IC_FACT_NET_MAXL layers; 4: ic_codec_*) */
 int ic_device_sync_check(void* stream); /* hipStreamQuery-free no-op launch test */
 
 /* ---- Conv2d (k x k, stride, zero pad): y = conv(x, w) + b, act 0=none 1=relu
@@ -467,6 +467,42 @@ int ic_images_u8_to_input(const unsigned char* x, long long sn, long long sh, lo
 int ic_sqdiff_fwd(const float* a, const float* b, long long n, float* out, void* stream);
 int ic_sqdiff_bwd(const float* a, const float* b, const float* g, long long n, float* ga, float* gb,
                   void* stream);
+
+/* ---- entropy coder: wave64-interleaved rANS over quantized CDF tables (the bitstream format is
+ *      specified in image_compression_amd/codec.py, the table rule in DESIGN.md).  Symbols are
+ *      int32 k in [-K, K], K <= IC_CODEC_KMAX; a table is [rows][2K+2] cumulative counts, 0 first,
+ *      strictly increasing, 65536 last.  A chunk is 64 * steps_per_chunk consecutive symbols coded
+ *      by one wavefront.  These entry points serve compress / decompress, not the training step;
+ *      ic_codec_symbolize is the one entry point of the library that waits for its stream. ---- */
+#define IC_CODEC_KMAX 2047  /* 2K+1 <= 4095 counts >= 1 inside a 16-bit total */
+#define IC_CODEC_MAXL 256   /* scale-table rows (uint8 row indices) */
+#define IC_CODEC_MAXR 65536 /* steps per chunk */
+/* sym[i] = (int)rintf(x[i]) and *kmax_dev = max |sym| (device int); copies it to *kmax_host and
+ * waits for the stream.  IC_ERR_ARG (with *kmax_host set) when it exceeds IC_CODEC_KMAX. */
+int ic_codec_symbolize(const float* x, long long n, int* sym, int* kmax_dev, int* kmax_host, void* stream);
+/* rows[i] = number of mids[0 .. L-2] (host fp32, ascending) strictly below sigma[i]: the nearest of L
+ * table scales when mids are the midpoints of neighbouring scales */
+int ic_codec_scale_index(const float* sigma, long long n, const float* mids, int L, unsigned char* rows,
+                         void* stream);
+/* pmf [rows][2K+1] fp32 -> cdf [rows][2K+2] uint32 (normalise, floor with every count >= 1,
+ * the remainder to the largest count) */
+int ic_codec_build_tables(const float* pmf, int rows, int K, unsigned int* cdf, void* stream);
+long long ic_codec_chunks(long long n, int steps_per_chunk);     /* ceil(n / (64 * steps_per_chunk)); 0: bad arguments */
+size_t ic_codec_encode_ws(long long n, int steps_per_chunk);     /* chunks * (2 * 64 * steps_per_chunk + 256) bytes */
+size_t ic_codec_compact_bytes(long long n, int steps_per_chunk); /* 4 * chunks + the encode workspace: the worst case */
+/* The row of symbol i is rows[i], or i % C where rows is NULL.  Each chunk is coded into its own slot of
+ * ws, ending at the slot's end; lengths[chunk] (device) = its bytes. */
+int ic_codec_encode(const int* sym, long long n, const unsigned char* rows, int C, const unsigned int* cdf,
+                    int nrows, int K, int steps_per_chunk, void* ws, size_t ws_bytes, unsigned int* lengths,
+                    void* stream);
+/* out = [lengths: chunks x u32 little endian][chunk 0][chunk 1]... (offsets: exclusive scan of lengths) */
+int ic_codec_compact(const void* ws, const unsigned int* lengths, long long n, int steps_per_chunk, void* out,
+                     size_t out_bytes, void* stream);
+/* in = the layout ic_codec_compact writes, in_bytes long (device); out[i] = symbol i as a float.  Reads of
+ * `in` stay inside each chunk's [begin, end) clamped to in_bytes, table searches inside the row: any
+ * payload decodes to some symbols in [-K, K]. */
+int ic_codec_decode(const void* in, size_t in_bytes, long long n, const unsigned char* rows, int C,
+                    const unsigned int* cdf, int nrows, int K, int steps_per_chunk, float* out, void* stream);
 
 #ifdef __cplusplus
 }
