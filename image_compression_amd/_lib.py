@@ -190,6 +190,18 @@ SIGNATURES = {
                                 c_void]),
     "ic_codec_compact": (c_int, [c_void, c_void, c_ll, c_int, c_void, c_size, c_void]),
     "ic_codec_decode": (c_int, [c_void, c_size, c_ll, c_void, c_int, c_void, c_int, c_int, c_int, c_void, c_void]),
+    # segmented coder and image borders of the per-image streams (additive to ic_version 4)
+    "ic_codec_seg_chunks": (c_ll, [c_int, c_ll, c_int]),
+    "ic_codec_encode_seg_ws": (c_size, [c_int, c_ll, c_int]),
+    "ic_codec_compact_seg_bytes": (c_size, [c_int, c_ll, c_int]),
+    "ic_codec_symbolize_seg": (c_int, [c_void, c_int, c_ll, c_void, c_void, P(c_int), c_void]),
+    "ic_codec_encode_seg": (c_int, [c_void, c_int, c_ll, c_void, c_int, c_void, c_size, c_int, P(c_int), P(c_ll),
+                                    c_void, c_int, c_void, c_size, c_void, c_void]),
+    "ic_codec_compact_seg": (c_int, [c_void, c_void, c_ll, c_int, c_void, c_size, c_void]),
+    "ic_codec_decode_seg": (c_int, [c_void, c_size, c_int, c_ll, c_void, c_int, c_void, c_size, c_int, P(c_int),
+                                    P(c_ll), c_void, c_int, c_void, c_void]),
+    "ic_pad_edge": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    "ic_crop_clamp": (c_int, [_ACT, c_int, c_int, c_void, c_void]),
 }
 
 _lib = None
@@ -206,6 +218,12 @@ def codec_ops():
         ops()
         _codec_ops = torch.ops.imgcomp_codec
     return _codec_ops
+
+
+def stream_ops():
+    """torch.ops.imgcomp_stream (the segmented coder and the image borders of the per-image streams)."""
+    ops()
+    return torch.ops.imgcomp_stream
 
 
 def ops():

@@ -55,6 +55,21 @@ Container (little endian), one call = one batch = one bytes object
     u64 symbols of z, u64 symbols of y, u32 chunks of z, u32 chunks of y,
     chunk lengths of z (u32 each), chunk lengths of y, payload of z, payload of y.
 y has N x latent x H/16 x W/16 symbols, z N x hyper x H/64 x W/64.
+
+Per-image container (little endian), one image = one bytes object (`compress_each`)
+------------------------------------------------------------------------------------
+An image of any size h x w >= 1 is padded at the bottom and the right to H = 64 * ceil(h / 64),
+W = 64 * ceil(w / 64) by replicating its last row and column, x_pad[c, i, j] = x[c, min(i, h-1),
+min(j, w-1)], and the padded image is coded; the decoder returns the top-left h x w of the
+reconstruction.  The two bitstreams are exactly the ones above for a batch of one: symbols of this
+image only in (h, w, c) order, K = the largest |symbol| of this image's tensor, chunks cut from the
+image's first symbol (no chunk holds symbols of two images), and the rows of y from
+sigma = h_s(z_hat) evaluated on this image alone (batch shape 1), whoever else is coded or decoded in
+the same call.
+    magic "ICRP", u16 format version (1), then the fields of the "ICRA" header from the arithmetic
+    tag to the chunk counts, with N = 1 and H, W the padded size,
+    u32 image height h, u32 image width w   (1 <= h <= H, H - h < 64; 1 <= w <= W, W - w < 64),
+    chunk lengths of z (u32 each), chunk lengths of y, payload of z, payload of y.
 """
 import math
 import struct
@@ -73,6 +88,10 @@ COMPUTE_DTYPES = ("fp32_split", "fp32", "bf16")
 Y_DOWN, Z_DOWN = 16, 64    # image pixels per latent / hyper-latent sample, each way
 
 _HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQII")
+
+IMAGE_MAGIC = b"ICRP"
+IMAGE_FORMAT_VERSION = 1
+_IMAGE_HEAD = struct.Struct(_HEAD.format + "II")   # the ICRA header's fields, then image height and width
 
 
 @dataclass
@@ -107,6 +126,18 @@ class Header:
     @property
     def nsym_y(self):
         return int(np.prod(self.y_shape, dtype=np.int64))
+
+
+@dataclass
+class ImageHeader(Header):
+    """Header of the per-image container: N = 1, H x W the padded size, height x width the image's."""
+    height: int
+    width: int
+
+
+def padded_size(h, w):
+    """(H, W): h and w rounded up to multiples of 64, the size that is coded."""
+    return -(-int(h) // Z_DOWN) * Z_DOWN, -(-int(w) // Z_DOWN) * Z_DOWN
 
 
 def num_chunks(nsym, R):
@@ -159,9 +190,8 @@ def _check_lengths(name, lens, nsym, R):
             raise ValueError(f"codec: {name} chunk {c} of {words} symbols cannot be {n} bytes long")
 
 
-def pack(h, lens_z, lens_y, payload_z, payload_y):
-    """One bytes object from the header, the two chunk-length tables and the two payloads."""
-    _check_header(h)
+def _pack_body(h, lens_z, lens_y, payload_z, payload_y):
+    """The checked length tables and payloads of a container, and the header fields both containers share."""
     lens_z = np.ascontiguousarray(lens_z, dtype="<u4")
     lens_y = np.ascontiguousarray(lens_y, dtype="<u4")
     payload_z, payload_y = bytes(payload_z), bytes(payload_y)
@@ -169,25 +199,30 @@ def pack(h, lens_z, lens_y, payload_z, payload_y):
     _check_lengths("y", lens_y, h.nsym_y, h.R)
     if int(lens_z.sum(dtype=np.uint64)) != len(payload_z) or int(lens_y.sum(dtype=np.uint64)) != len(payload_y):
         raise ValueError("codec: chunk lengths do not add up to the payload")
-    head = _HEAD.pack(MAGIC, FORMAT_VERSION, COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W,
-                      h.latent_channels, h.hyper_channels, h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y,
-                      h.nsym_z, h.nsym_y, len(lens_z), len(lens_y))
-    return b"".join((head, lens_z.tobytes(), lens_y.tobytes(), payload_z, payload_y))
+    fields = (COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W, h.latent_channels, h.hyper_channels,
+              h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y, h.nsym_z, h.nsym_y, len(lens_z), len(lens_y))
+    return fields, (lens_z.tobytes(), lens_y.tobytes(), payload_z, payload_y)
 
 
-def parse(data, abi, compute_dtype):
-    """(Header, lens_z, lens_y, payload_z, payload_y) of a container made by `pack`; `abi` and
-    `compute_dtype` are the running build's ic_version() and the model's arithmetic, which the
-    stream must match.  Raises ValueError on anything inconsistent; nothing is launched here."""
+def pack(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object from the header, the two chunk-length tables and the two payloads."""
+    _check_header(h)
+    fields, body = _pack_body(h, lens_z, lens_y, payload_z, payload_y)
+    return b"".join((_HEAD.pack(MAGIC, FORMAT_VERSION, *fields),) + body)
+
+
+def _parse(data, abi, compute_dtype, head, magic, version, make_header):
+    """What `parse` and `parse_image` share: the header `head` with its magic and version, the checks of the
+    header `make_header(common fields, extra fields)` returns, the length tables and the payloads."""
     data = bytes(data)
-    if len(data) < _HEAD.size:
-        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({_HEAD.size})")
-    (magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz,
-     ncy) = _HEAD.unpack_from(data, 0)
-    if magic != MAGIC:
-        raise ValueError(f"codec: bad magic {magic!r}")
-    if ver != FORMAT_VERSION:
-        raise ValueError(f"codec: format version {ver}, this build reads {FORMAT_VERSION}")
+    if len(data) < head.size:
+        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({head.size})")
+    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz, ncy,
+     *extra) = head.unpack_from(data, 0)
+    if s_magic != magic:
+        raise ValueError(f"codec: bad magic {s_magic!r}")
+    if ver != version:
+        raise ValueError(f"codec: format version {ver}, this build reads {version}")
     if dt >= len(COMPUTE_DTYPES):
         raise ValueError(f"codec: unknown arithmetic tag {dt}")
     if COMPUTE_DTYPES[dt] != compute_dtype:
@@ -195,13 +230,12 @@ def parse(data, abi, compute_dtype):
                          f"{compute_dtype!r}")
     if s_abi != abi:
         raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
-    h = Header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky)
-    _check_header(h)
+    h = make_header((N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky), extra)
     if nz != h.nsym_z or ny != h.nsym_y:
         raise ValueError("codec: symbol counts do not match the batch shape")
     if ncz != num_chunks(nz, R) or ncy != num_chunks(ny, R):
         raise ValueError("codec: chunk counts do not match the symbol counts")
-    off = _HEAD.size
+    off = head.size
     if len(data) < off + 4 * (ncz + ncy):
         raise ValueError("codec: buffer ends inside the chunk-length tables")
     lens_z = np.frombuffer(data, dtype="<u4", count=ncz, offset=off)
@@ -213,6 +247,67 @@ def parse(data, abi, compute_dtype):
     if off + bz + by != len(data):
         raise ValueError(f"codec: chunk lengths add up to {bz + by} payload bytes, the buffer holds {len(data) - off}")
     return h, lens_z, lens_y, data[off:off + bz], data[off + bz:]
+
+
+def parse(data, abi, compute_dtype):
+    """(Header, lens_z, lens_y, payload_z, payload_y) of a container made by `pack`; `abi` and
+    `compute_dtype` are the running build's ic_version() and the model's arithmetic, which the
+    stream must match.  Raises ValueError on anything inconsistent; nothing is launched here."""
+    def make(common, _extra):
+        h = Header(*common)
+        _check_header(h)
+        return h
+    return _parse(data, abi, compute_dtype, _HEAD, MAGIC, FORMAT_VERSION, make)
+
+
+def _check_image_header(h):
+    _check_header(h)
+    if h.N != 1:
+        raise ValueError(f"codec: a per-image stream holds one image, not {h.N}")
+    for name, full, part in (("height", h.H, h.height), ("width", h.W, h.width)):
+        if not 1 <= part <= full or full - part >= Z_DOWN:
+            raise ValueError(f"codec: image {name} {part} does not pad to {full}")
+
+
+def image_fixed_bytes(h):
+    """`fixed_bytes` of a per-image container."""
+    return fixed_bytes(h) + _IMAGE_HEAD.size - _HEAD.size
+
+
+def pack_image(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object for one image from its ImageHeader, chunk-length tables and payloads."""
+    _check_image_header(h)
+    fields, body = _pack_body(h, lens_z, lens_y, payload_z, payload_y)
+    return b"".join((_IMAGE_HEAD.pack(IMAGE_MAGIC, IMAGE_FORMAT_VERSION, *fields, h.height, h.width),) + body)
+
+
+def parse_image(data, abi, compute_dtype):
+    """(ImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_image`: the
+    checks of `parse`, and those of the image size.  Nothing is launched here."""
+    def make(common, extra):
+        h = ImageHeader(*common, *extra)
+        _check_image_header(h)
+        return h
+    return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, make)
+
+
+def split_packed_seg(packed, nseg, seg_len, R):
+    """[(lengths, payload bytes)] per segment of the segmented coder's output buffer
+    [all lengths][all payload][padding]: stream s is found by summing the lengths before it."""
+    packed = np.asarray(packed, dtype=np.uint8)
+    cps = num_chunks(seg_len, R)
+    lens = packed[:4 * cps * nseg].view("<u4").copy().reshape(nseg, cps)
+    ends = np.cumsum(lens.sum(axis=1, dtype=np.uint64))
+    if 4 * cps * nseg + int(ends[-1]) > packed.size:
+        raise RuntimeError("codec: the coder reported more bytes than its buffer holds")
+    body = packed[4 * cps * nseg:]
+    return [(lens[s], body[int(ends[s - 1]) if s else 0:int(ends[s])].tobytes()) for s in range(nseg)]
+
+
+def join_packed_seg(parts):
+    """The segmented decoder's input [all lengths][all payload] from [(lengths, payload)] per segment."""
+    lens = b"".join(np.ascontiguousarray(l, dtype="<u4").tobytes() for l, _ in parts)
+    return np.frombuffer(lens + b"".join(bytes(p) for _, p in parts), dtype=np.uint8)
 
 
 def split_packed(packed, nsym, R):

@@ -11,7 +11,10 @@
 //     words in the order the decoder takes them: ascending step, ascending lane.
 // The decoder never reads outside its chunk's [begin, end) nor outside a table
 // row, whatever the payload holds: wrong input gives wrong symbols only.
+// The segmented entry points (ic_codec_*_seg) code several images' symbols, each with its own K and
+// table, in one launch; a chunk is coded by the same device function either way.
 #include <algorithm>
+#include <vector>
 
 #include "common.h"
 #include "../../include/imgcomp.h"
@@ -25,25 +28,49 @@ constexpr size_t CODEC_LDS_BYTES = 49152;            // tables up to this size a
 // ------------------------------------------------------------------ symbolize
 // q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and max|q| by one
 // integer atomic per block (integer max is order-independent: deterministic).
-__global__ void codec_symbolize_k(const float* __restrict__ x, long long n, int* __restrict__ sym,
-                                  int* __restrict__ kmax) {
+__device__ __forceinline__ int symbol_of(float v) {
+  // |q| beyond 2^30 (or NaN) only has to be reported as too large, not represented
+  const float q = fminf(fmaxf(rintf(v), -1073741824.f), 1073741824.f);
+  return (q == q) ? (int)q : 1073741824;
+}
+
+// the block's maximum of m, in thread 0
+__device__ __forceinline__ int block_max(int m) {
   __shared__ int smax[16];
-  int m = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    // |q| beyond 2^30 (or NaN) only has to be reported as too large, not represented
-    const float q = fminf(fmaxf(rintf(x[i]), -1073741824.f), 1073741824.f);
-    const int k = (q == q) ? (int)q : 1073741824;
-    sym[i] = k;
-    m = max(m, k < 0 ? -k : k);
-  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
   if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0)
     for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = max(m, smax[w]);
-    atomicMax(kmax, m);
+  return m;
+}
+
+__global__ void codec_symbolize_k(const float* __restrict__ x, long long n, int* __restrict__ sym,
+                                  int* __restrict__ kmax) {
+  int m = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const int k = symbol_of(x[i]);
+    sym[i] = k;
+    m = max(m, k < 0 ? -k : k);
   }
+  m = block_max(m);
+  if (threadIdx.x == 0) atomicMax(kmax, m);
+}
+
+// nseg segments of seg_len values back to back: blockIdx.y = segment, kmax[segment] = its max |q|
+__global__ void codec_symbolize_seg_k(const float* __restrict__ x, long long seg_len, int* __restrict__ sym,
+                                      int* __restrict__ kmax) {
+  const long long base = (long long)blockIdx.y * seg_len;
+  int m = 0;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < seg_len;
+       i += (long long)gridDim.x * blockDim.x) {
+    const int k = symbol_of(x[base + i]);
+    sym[base + i] = k;
+    m = max(m, k < 0 ? -k : k);
+  }
+  m = block_max(m);
+  if (threadIdx.x == 0) atomicMax(kmax + blockIdx.y, m);
 }
 
 // ------------------------------------------------------------------ scale index
@@ -128,6 +155,8 @@ __global__ void codec_tables_k(const float* __restrict__ pmf, int M, uint32_t* _
 }
 
 // ------------------------------------------------------------------ rANS
+__host__ __device__ inline size_t table_bytes(int nrows, int K) { return (size_t)nrows * (2 * K + 2) * sizeof(uint32_t); }
+
 struct CodecArgs {
   long long n;                 // symbols of the tensor
   const unsigned char* rows;   // per-symbol table row, or null: row = global index % C
@@ -155,21 +184,17 @@ __device__ __forceinline__ int row_of(const CodecArgs& a, long long g) {
 // [2^16, 2^32) each emit their low 16 bits first.  Words are laid down from the slot's end towards its
 // start, a step's emitters in ascending lane order, so that read forward they come in ascending step,
 // ascending lane; the 64 final states go in front.  slot = 2*64*R + 256 bytes is the worst case (one
-// word per symbol).  lengths[chunk] = bytes used; they end at the slot's end.
+// word per symbol).  *length = bytes used; they end at the slot's end.
+// The chunk holds the nc symbols from global index c0 on; a.cdf is the table of those symbols.
 template <bool LDS>
-__global__ void __launch_bounds__(64) codec_encode_k(const int* __restrict__ sym, CodecArgs a,
-                                                     unsigned short* __restrict__ scratch,
-                                                     uint32_t* __restrict__ lengths) {
-  extern __shared__ uint32_t lds[];
+__device__ __forceinline__ void encode_chunk(const int* __restrict__ sym, const CodecArgs& a, long long c0, int nc,
+                                             unsigned short* __restrict__ slot, uint32_t* __restrict__ length,
+                                             uint32_t* lds) {
   const uint32_t* tab = stage_tables<LDS>(a, lds);
   const int lane = threadIdx.x;
   const int M1 = 2 * a.K + 2;
-  const long long per = 64ll * a.R;
-  const long long c0 = (long long)blockIdx.x * per;
-  const int nc = (int)min(per, a.n - c0);
   const int steps = (nc + 63) >> 6;
-  const size_t slot_words = (size_t)per + 128;
-  unsigned short* slot = scratch + (size_t)blockIdx.x * slot_words;
+  const size_t slot_words = (size_t)64 * a.R + 128;
   long long ptr = (long long)slot_words;
   uint32_t x = RANS_L;
   const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
@@ -197,7 +222,55 @@ __global__ void __launch_bounds__(64) codec_encode_k(const int* __restrict__ sym
   ptr -= 128;
   slot[ptr + 2 * lane] = (unsigned short)(x & 0xffffu);
   slot[ptr + 2 * lane + 1] = (unsigned short)(x >> 16);
-  if (lane == 0) lengths[blockIdx.x] = (uint32_t)((slot_words - (size_t)ptr) * 2);
+  if (lane == 0) *length = (uint32_t)((slot_words - (size_t)ptr) * 2);
+}
+
+template <bool LDS>
+__global__ void __launch_bounds__(64) codec_encode_k(const int* __restrict__ sym, CodecArgs a,
+                                                     unsigned short* __restrict__ scratch,
+                                                     uint32_t* __restrict__ lengths) {
+  extern __shared__ uint32_t lds[];
+  const long long per = 64ll * a.R;
+  const long long c0 = (long long)blockIdx.x * per;
+  encode_chunk<LDS>(sym, a, c0, (int)min(per, a.n - c0), scratch + (size_t)blockIdx.x * ((size_t)per + 128),
+                    lengths + blockIdx.x, lds);
+}
+
+// Segmented coding: nseg segments (images) of seg_len symbols back to back, each with its own K and
+// table.  kt (device) holds (K, word offset of the table in `pool`) per segment; chunks never straddle a
+// segment (cps chunks each, the last possibly short); block = (segment, chunk) in that order.
+struct SegArgs {
+  long long seg_len;
+  const unsigned char* rows;   // per-symbol row over all segments, or null: row = global index % C
+  int C;                       // (segment starts are multiples of C: the global index serves)
+  const uint32_t* pool;
+  const int* kt;
+  int nrows, R, cps;
+};
+
+// the block's segment as the CodecArgs of its table; c0 / nc = the chunk's first symbol and size
+__device__ __forceinline__ CodecArgs seg_chunk(const SegArgs& s, long long* c0, int* nc) {
+  const int seg = (int)(blockIdx.x / (unsigned)s.cps), lc = (int)(blockIdx.x % (unsigned)s.cps);
+  const long long per = 64ll * s.R, l0 = (long long)lc * per;
+  *c0 = (long long)seg * s.seg_len + l0;
+  *nc = (int)min(per, s.seg_len - l0);
+  return CodecArgs{s.seg_len, s.rows, s.C, s.pool + (uint32_t)s.kt[2 * seg + 1], s.nrows, s.kt[2 * seg], s.R};
+}
+
+// A block stages its own segment's table in LDS when it fits and reads it where it is otherwise: one
+// image with a large K does not cost the others their LDS tables.  Same arithmetic either way.
+__global__ void __launch_bounds__(64) codec_encode_seg_k(const int* __restrict__ sym, SegArgs s,
+                                                         unsigned short* __restrict__ scratch,
+                                                         uint32_t* __restrict__ lengths) {
+  extern __shared__ uint32_t lds[];
+  long long c0;
+  int nc;
+  const CodecArgs a = seg_chunk(s, &c0, &nc);
+  unsigned short* slot = scratch + (size_t)blockIdx.x * (64ull * s.R + 128);
+  if (table_bytes(a.nrows, a.K) <= CODEC_LDS_BYTES)
+    encode_chunk<true>(sym, a, c0, nc, slot, lengths + blockIdx.x, lds);
+  else
+    encode_chunk<false>(sym, a, c0, nc, slot, lengths + blockIdx.x, lds);
 }
 
 // out = [lengths: nchunks x u32][chunk 0 bytes][chunk 1 bytes]...; block = chunk; its offset is the
@@ -224,19 +297,15 @@ __global__ void codec_compact_k(const unsigned short* __restrict__ scratch, cons
   }
 }
 
-// The mirror of codec_encode_k.  in = the compact buffer ([lengths][payload], in_words 16-bit words in
-// all).  Every read of `in` is guarded by the chunk's [begin, end), itself clamped to the buffer; the
-// search stays inside the symbol's row.
-template <bool LDS>
-__global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __restrict__ in, size_t in_words,
-                                                     int nchunks, CodecArgs a, float* __restrict__ out) {
-  extern __shared__ uint32_t lds[];
+// [begin, end) of chunk `chunk` in the compact buffer `in` ([lengths: nchunks x u32][payload], in_words
+// 16-bit words in all), in words and clamped to the buffer.  The whole block calls it.
+__device__ __forceinline__ void chunk_span(const unsigned short* __restrict__ in, size_t in_words, int nchunks,
+                                           int chunk, size_t* begin, size_t* end) {
   __shared__ unsigned long long part[64];
-  const uint32_t* tab = stage_tables<LDS>(a, lds);
   const int lane = threadIdx.x;
   const uint32_t* lens = reinterpret_cast<const uint32_t*>(in);  // 2 * nchunks <= in_words (checked by the host)
   unsigned long long s = 0;
-  for (int c = lane; c < (int)blockIdx.x; c += 64) s += lens[c];
+  for (int c = lane; c < chunk; c += 64) s += lens[c];
   part[lane] = s;
   __syncthreads();
   if (lane == 0) {
@@ -245,16 +314,23 @@ __global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __res
     part[0] = tot;
   }
   __syncthreads();
-  const size_t begin = min((size_t)(2ull * nchunks + part[0] / 2), in_words);
-  const size_t end = min(begin + (size_t)lens[blockIdx.x] / 2, in_words);
+  *begin = min((size_t)(2ull * nchunks + part[0] / 2), in_words);
+  *end = min(*begin + (size_t)lens[chunk] / 2, in_words);
+}
+
+// The mirror of encode_chunk.  Every read of `in` is guarded by the chunk's [begin, end); the search
+// stays inside the symbol's row.
+template <bool LDS>
+__device__ __forceinline__ void decode_chunk(const unsigned short* __restrict__ in, size_t begin, size_t end,
+                                             const CodecArgs& a, long long c0, int nc, float* __restrict__ out,
+                                             uint32_t* lds) {
+  const uint32_t* tab = stage_tables<LDS>(a, lds);
+  const int lane = threadIdx.x;
   auto word = [&](size_t w) -> uint32_t { return w < end ? (uint32_t)in[w] : 0u; };
 
   const int M = 2 * a.K + 1, M1 = M + 1;
   int iters = 0;
   while ((1 << iters) < M) ++iters;
-  const long long per = 64ll * a.R;
-  const long long c0 = (long long)blockIdx.x * per;
-  const int nc = (int)min(per, a.n - c0);
   const int steps = (nc + 63) >> 6;
   uint32_t x = word(begin + 2 * lane) | (word(begin + 2 * lane + 1) << 16);
   size_t cur = begin + 128;
@@ -283,13 +359,37 @@ __global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __res
   }
 }
 
+template <bool LDS>
+__global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __restrict__ in, size_t in_words,
+                                                     int nchunks, CodecArgs a, float* __restrict__ out) {
+  extern __shared__ uint32_t lds[];
+  size_t begin, end;
+  chunk_span(in, in_words, nchunks, (int)blockIdx.x, &begin, &end);
+  const long long per = 64ll * a.R;
+  const long long c0 = (long long)blockIdx.x * per;
+  decode_chunk<LDS>(in, begin, end, a, c0, (int)min(per, a.n - c0), out, lds);
+}
+
+// in = the concatenation of the segments' length tables, then of their payloads, (segment, chunk) order
+__global__ void __launch_bounds__(64) codec_decode_seg_k(const unsigned short* __restrict__ in, size_t in_words,
+                                                         int nchunks, SegArgs s, float* __restrict__ out) {
+  extern __shared__ uint32_t lds[];
+  size_t begin, end;
+  chunk_span(in, in_words, nchunks, (int)blockIdx.x, &begin, &end);
+  long long c0;
+  int nc;
+  const CodecArgs a = seg_chunk(s, &c0, &nc);
+  if (table_bytes(a.nrows, a.K) <= CODEC_LDS_BYTES)
+    decode_chunk<true>(in, begin, end, a, c0, nc, out, lds);
+  else
+    decode_chunk<false>(in, begin, end, a, c0, nc, out, lds);
+}
+
 bool codec_args_ok(long long n, const void* rows, int C, int nrows, int K, int R) {
   if (n < 1 || nrows < 1 || K < 0 || K > CODEC_KMAX || R < 1 || R > IC_CODEC_MAXR) return false;
   if (!rows && (C < 1 || C > nrows)) return false;
   return (n + 64ll * R - 1) / (64ll * R) <= 0x7fffffffll;
 }
-
-size_t table_bytes(int nrows, int K) { return (size_t)nrows * (2 * K + 2) * sizeof(uint32_t); }
 
 }  // namespace
 
@@ -387,6 +487,130 @@ int ic_codec_decode(const void* in, size_t in_bytes, long long n, const unsigned
   else
     hipLaunchKernelGGL(codec_decode_k<false>, dim3(chunks), dim3(64), 0, (hipStream_t)stream,
                        (const unsigned short*)in, in_bytes / 2, chunks, a, out);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+// ---------------------------------------------------------------- segmented entry points
+long long ic_codec_seg_chunks(int nseg, long long seg_len, int steps_per_chunk) {
+  const long long cps = ic_codec_chunks(seg_len, steps_per_chunk);
+  if (nseg < 1 || cps < 1 || seg_len > 0x7fffffffffffffffll / nseg || cps > 0x7fffffffll / nseg) return 0;
+  return cps * nseg;
+}
+
+size_t ic_codec_encode_seg_ws(int nseg, long long seg_len, int steps_per_chunk) {
+  const long long c = ic_codec_seg_chunks(nseg, seg_len, steps_per_chunk);
+  return c < 1 ? 0 : (size_t)c * (128ull * steps_per_chunk + 256);
+}
+
+size_t ic_codec_compact_seg_bytes(int nseg, long long seg_len, int steps_per_chunk) {
+  const long long c = ic_codec_seg_chunks(nseg, seg_len, steps_per_chunk);
+  return c < 1 ? 0 : (size_t)c * 4 + ic_codec_encode_seg_ws(nseg, seg_len, steps_per_chunk);
+}
+
+int ic_codec_symbolize_seg(const float* x, int nseg, long long seg_len, int* sym, int* kmax_dev, int* kmax_host,
+                           void* stream) {
+  if (!x || !sym || !kmax_dev || !kmax_host || nseg < 1 || nseg > 65535 || seg_len < 1 ||
+      seg_len > 0x7fffffffffffffffll / nseg)
+    return IC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  hipError_t e = hipMemsetAsync(kmax_dev, 0, sizeof(int) * nseg, st);
+  if (e != hipSuccess) return (int)e;
+  const int blocks = (int)std::min<long long>((seg_len + 255) / 256, 1024);
+  hipLaunchKernelGGL(codec_symbolize_seg_k, dim3(blocks, nseg), dim3(256), 0, st, x, seg_len, sym, kmax_dev);
+  IC_CHECK_LAUNCH();
+  e = hipMemcpyAsync(kmax_host, kmax_dev, sizeof(int) * nseg, hipMemcpyDeviceToHost, st);
+  if (e != hipSuccess) return (int)e;
+  e = hipStreamSynchronize(st);
+  if (e != hipSuccess) return (int)e;
+  for (int s = 0; s < nseg; ++s)
+    if (kmax_host[s] > CODEC_KMAX) return IC_ERR_ARG;
+  return IC_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// The checks of the segmented coder, before any launch: every segment's K in range and its table inside
+// the pool; without per-symbol rows the row is the global index % C, which needs segment starts that are
+// multiples of C.  *lds = the dynamic LDS of the launch: the largest table that is staged.
+bool codec_seg_ok(int nseg, long long seg_len, const void* rows, int C, size_t pool_words, int nrows, const int* seg_k,
+                  const long long* seg_off, int R, size_t* lds) {
+  if (!seg_k || !seg_off || nrows < 1 || ic_codec_seg_chunks(nseg, seg_len, R) < 1) return false;
+  if (!rows && (C < 1 || C > nrows || seg_len % C)) return false;
+  *lds = 0;
+  for (int s = 0; s < nseg; ++s) {
+    if (seg_k[s] < 0 || seg_k[s] > CODEC_KMAX || seg_off[s] < 0 || seg_off[s] > 0x7fffffffll) return false;
+    const size_t tb = table_bytes(nrows, seg_k[s]);
+    if ((size_t)seg_off[s] + tb / sizeof(uint32_t) > pool_words) return false;
+    if (tb <= CODEC_LDS_BYTES) *lds = std::max(*lds, tb);
+  }
+  return true;
+}
+
+// (K, table offset) per segment -> seg_dev; the host arrays are consumed before this returns (a copy from
+// pageable memory is staged by the runtime)
+hipError_t seg_upload(int nseg, const int* seg_k, const long long* seg_off, int* seg_dev, hipStream_t st) {
+  std::vector<int> kt(2 * (size_t)nseg);
+  for (int s = 0; s < nseg; ++s) {
+    kt[2 * s] = seg_k[s];
+    kt[2 * s + 1] = (int)seg_off[s];
+  }
+  return hipMemcpyAsync(seg_dev, kt.data(), kt.size() * sizeof(int), hipMemcpyHostToDevice, st);
+}
+
+}  // namespace
+
+extern "C" {
+
+int ic_codec_encode_seg(const int* sym, int nseg, long long seg_len, const unsigned char* rows, int C,
+                        const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                        const long long* seg_off, int* seg_dev, int steps_per_chunk, void* ws, size_t ws_bytes,
+                        unsigned int* lengths, void* stream) {
+  size_t lds = 0;
+  if (!sym || !pool || !seg_dev || !ws || !lengths ||
+      !codec_seg_ok(nseg, seg_len, rows, C, pool_words, nrows, seg_k, seg_off, steps_per_chunk, &lds))
+    return IC_ERR_ARG;
+  if (ws_bytes < ic_codec_encode_seg_ws(nseg, seg_len, steps_per_chunk)) return IC_ERR_WORKSPACE;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = seg_upload(nseg, seg_k, seg_off, seg_dev, st);
+  if (e != hipSuccess) return (int)e;
+  const int cps = (int)ic_codec_chunks(seg_len, steps_per_chunk);
+  const SegArgs a{seg_len, rows, C, pool, seg_dev, nrows, steps_per_chunk, cps};
+  hipLaunchKernelGGL(codec_encode_seg_k, dim3((unsigned)(cps * nseg)), dim3(64), lds, st, sym, a, (unsigned short*)ws,
+                     lengths);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_compact_seg(const void* ws, const unsigned int* lengths, long long chunks, int steps_per_chunk, void* out,
+                         size_t out_bytes, void* stream) {
+  if (!ws || !lengths || !out || chunks < 1 || chunks > 0x7fffffffll || steps_per_chunk < 1 ||
+      steps_per_chunk > IC_CODEC_MAXR)
+    return IC_ERR_ARG;
+  if (out_bytes < (size_t)chunks * (4 + 128ull * steps_per_chunk + 256)) return IC_ERR_WORKSPACE;
+  hipLaunchKernelGGL(codec_compact_k, dim3((unsigned)chunks), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)ws, lengths, (int)chunks, steps_per_chunk, (unsigned short*)out);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_decode_seg(const void* in, size_t in_bytes, int nseg, long long seg_len, const unsigned char* rows, int C,
+                        const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                        const long long* seg_off, int* seg_dev, int steps_per_chunk, float* out, void* stream) {
+  size_t lds = 0;
+  if (!in || !pool || !seg_dev || !out ||
+      !codec_seg_ok(nseg, seg_len, rows, C, pool_words, nrows, seg_k, seg_off, steps_per_chunk, &lds))
+    return IC_ERR_ARG;
+  const int cps = (int)ic_codec_chunks(seg_len, steps_per_chunk), chunks = cps * nseg;
+  if (in_bytes < 4ull * chunks) return IC_ERR_ARG;  // the length tables themselves must be inside the buffer
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = seg_upload(nseg, seg_k, seg_off, seg_dev, st);
+  if (e != hipSuccess) return (int)e;
+  const SegArgs a{seg_len, rows, C, pool, seg_dev, nrows, steps_per_chunk, cps};
+  hipLaunchKernelGGL(codec_decode_seg_k, dim3((unsigned)chunks), dim3(64), lds, st, (const unsigned short*)in,
+                     in_bytes / 2, chunks, a, out);
   IC_CHECK_LAUNCH();
   return IC_OK;
 }

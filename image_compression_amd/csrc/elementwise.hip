@@ -80,6 +80,27 @@ __global__ void bound_bwd_k(const float* x, const float* g, long long n, float b
   }
 }
 
+// y (N*C planes of Hp x Wp, dense) = x (planes of h x w, dense) with the last row / column replicated
+__global__ void pad_edge_k(const float* __restrict__ x, long long n, int h, int w, int Hp, int Wp,
+                           float* __restrict__ y) {
+  GRID_STRIDE(i, n) {
+    const int j = (int)(i % Wp), r = (int)((i / Wp) % Hp);
+    const long long p = i / ((long long)Wp * Hp);
+    y[i] = x[(p * h + min(r, h - 1)) * w + min(j, w - 1)];
+  }
+}
+// y (N, C, h, w dense) = the two bound_fwd_k expressions (upper 1, then lower 0) on the top-left h x w of x
+__global__ void crop_clamp_k(const float* __restrict__ x, long long sn, long long sc, long long sh, long long sw,
+                             long long n, int C, int h, int w, float* __restrict__ y) {
+  GRID_STRIDE(i, n) {
+    const int j = (int)(i % w), r = (int)((i / w) % h);
+    const long long p = i / ((long long)w * h);
+    const float v = x[(p / C) * sn + (p % C) * sc + r * sh + j * sw];
+    const float u = v < 1.f ? v : 1.f;
+    y[i] = u > 0.f ? u : 0.f;
+  }
+}
+
 __global__ void relu_fwd_k(const float* x, long long n, float* y) {
   GRID_STRIDE(i, n) {
     const float v = x[i];
@@ -279,6 +300,24 @@ int ic_bound_fwd(const float* x, long long n, float bound, int upper, float* y, 
 }
 int ic_bound_bwd(const float* x, const float* g, long long n, float bound, int upper, float* gx, void* stream) {
   hipLaunchKernelGGL(bound_bwd_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, g, n, bound, upper, gx);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+int ic_pad_edge(const float* x, int N, int C, int h, int w, int Hp, int Wp, float* y, void* stream) {
+  if (!x || !y || N < 1 || C < 1 || h < 1 || w < 1 || Hp < h || Wp < w) return IC_ERR_ARG;
+  const long long planes = (long long)N * C;
+  if ((long long)Hp * Wp > 0x7fffffffffffffffll / planes) return IC_ERR_ARG;
+  const long long n = planes * Hp * Wp;
+  hipLaunchKernelGGL(pad_edge_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x, n, h, w, Hp, Wp, y);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+int ic_crop_clamp(const ic_act* x, int h, int w, float* y, void* stream) {
+  if (!x || !x->data || !y || x->n < 1 || x->c < 1 || h < 1 || w < 1 || h > x->h || w > x->w) return IC_ERR_ARG;
+  if (x->sn < 0 || x->sc < 0 || x->sh < 0 || x->sw < 0) return IC_ERR_ARG;
+  const long long n = (long long)x->n * x->c * h * w;
+  hipLaunchKernelGGL(crop_clamp_k, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, (const float*)x->data, x->sn,
+                     x->sc, x->sh, x->sw, n, x->c, h, w, y);
   IC_CHECK_LAUNCH();
   return IC_OK;
 }

@@ -1239,6 +1239,142 @@ Tensor codec_decode_meta(const Tensor& packed, int64_t n, const std::optional<Te
   return at::empty({n}, packed.options().dtype(at::kFloat));
 }
 
+// ---------------------------------------------------------------- per-image streams (imgcomp_stream)
+// The segmented coder: nseg images' symbols back to back, K and table (word offset into `pool`) per image.
+struct SegTables {
+  std::vector<int> k;
+  std::vector<long long> off;
+};
+
+SegTables seg_tables(int64_t nseg, at::IntArrayRef seg_k, at::IntArrayRef seg_off) {
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && (int64_t)seg_k.size() == nseg && (int64_t)seg_off.size() == nseg,
+              "imgcomp_stream: one K and one table offset per segment");
+  SegTables t;
+  for (int64_t s = 0; s < nseg; ++s) {
+    TORCH_CHECK(seg_k[s] >= 0 && seg_k[s] <= IC_CODEC_KMAX, "imgcomp_stream: K of segment ", s, " is ", seg_k[s],
+                ", the coder's limit is ", IC_CODEC_KMAX);
+    t.k.push_back((int)seg_k[s]);
+    t.off.push_back(seg_off[s]);
+  }
+  return t;
+}
+
+std::tuple<Tensor, std::vector<int64_t>> stream_symbolize_seg(const Tensor& x, int64_t nseg) {
+  check_dense(x, "x");
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && x.numel() > 0 && x.numel() % nseg == 0,
+              "imgcomp_stream: ", x.numel(), " values do not make ", nseg, " equal segments");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor sym = at::empty({x.numel()}, x.options().dtype(at::kInt));
+  Tensor kd = at::empty({nseg}, x.options().dtype(at::kInt));
+  std::vector<int> kmax((size_t)nseg, 0);
+  const int rc = ic_codec_symbolize_seg(x.data_ptr<float>(), (int)nseg, x.numel() / nseg, sym.data_ptr<int>(),
+                                        kd.data_ptr<int>(), kmax.data(), stream_of(x));
+  if (rc == IC_ERR_ARG)
+    for (int64_t s = 0; s < nseg; ++s)
+      TORCH_CHECK_VALUE(kmax[s] <= IC_CODEC_KMAX, "imgcomp_stream: image ", s, " has a symbol of magnitude ", kmax[s],
+                        ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "codec_symbolize_seg");
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
+// [lengths: all chunks x u32][payload], (segment, chunk) order, padded to the worst case
+Tensor stream_encode_seg(const Tensor& sym, int64_t nseg, const std::optional<Tensor>& rows, int64_t C, const Tensor& pool,
+                         int64_t nrows, at::IntArrayRef seg_k, at::IntArrayRef seg_off, int64_t steps) {
+  check_codec(sym, at::kInt, "sym");
+  check_codec(pool, at::kInt, "table pool");
+  const SegTables t = seg_tables(nseg, seg_k, seg_off);
+  const int64_t n = sym.numel();
+  TORCH_CHECK(n > 0 && n % nseg == 0, "imgcomp_stream: ", n, " symbols do not make ", nseg, " equal segments");
+  const unsigned char* rp = codec_rows(rows, n);
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR, "imgcomp_stream: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  const int64_t seg_len = n / nseg, chunks = ic_codec_seg_chunks((int)nseg, seg_len, (int)steps);
+  TORCH_CHECK(chunks > 0, "imgcomp_stream: too many chunks");
+  const size_t nb = ic_codec_encode_seg_ws((int)nseg, seg_len, (int)steps);
+  const size_t ob = ic_codec_compact_seg_bytes((int)nseg, seg_len, (int)steps);
+  Tensor ws = at::empty({(int64_t)nb}, sym.options().dtype(at::kByte));
+  Tensor lens = at::empty({chunks}, sym.options());
+  Tensor kt = at::empty({2 * nseg}, sym.options());
+  Tensor out = at::empty({(int64_t)ob}, sym.options().dtype(at::kByte));
+  check_rc(ic_codec_encode_seg(sym.data_ptr<int>(), (int)nseg, seg_len, rp, (int)C,
+                               (const unsigned int*)pool.data_ptr<int>(), (size_t)pool.numel(), (int)nrows, t.k.data(),
+                               t.off.data(), kt.data_ptr<int>(), (int)steps, ws.data_ptr(), nb,
+                               (unsigned int*)lens.data_ptr<int>(), stream_of(sym)),
+           "codec_encode_seg");
+  check_rc(ic_codec_compact_seg(ws.data_ptr(), (const unsigned int*)lens.data_ptr<int>(), chunks, (int)steps,
+                                out.data_ptr(), ob, stream_of(sym)),
+           "codec_compact_seg");
+  return out;
+}
+
+Tensor stream_decode_seg(const Tensor& packed, int64_t nseg, int64_t seg_len, const std::optional<Tensor>& rows, int64_t C,
+                         const Tensor& pool, int64_t nrows, at::IntArrayRef seg_k, at::IntArrayRef seg_off,
+                         int64_t steps) {
+  check_codec(packed, at::kByte, "packed");
+  check_codec(pool, at::kInt, "table pool");
+  const SegTables t = seg_tables(nseg, seg_k, seg_off);
+  TORCH_CHECK(seg_len > 0 && seg_len <= INT64_MAX / nseg, "imgcomp_stream: no symbols");
+  const unsigned char* rp = codec_rows(rows, nseg * seg_len);
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR, "imgcomp_stream: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  TORCH_CHECK(((uintptr_t)packed.data_ptr() & 3) == 0, "imgcomp_stream: packed buffer must be 4-byte aligned");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(packed.device());
+  Tensor out = at::empty({nseg * seg_len}, packed.options().dtype(at::kFloat));
+  Tensor kt = at::empty({2 * nseg}, packed.options().dtype(at::kInt));
+  check_rc(ic_codec_decode_seg(packed.data_ptr(), (size_t)packed.numel(), (int)nseg, seg_len, rp, (int)C,
+                               (const unsigned int*)pool.data_ptr<int>(), (size_t)pool.numel(), (int)nrows, t.k.data(),
+                               t.off.data(), kt.data_ptr<int>(), (int)steps, out.data_ptr<float>(), stream_of(packed)),
+           "codec_decode_seg");
+  return out;
+}
+
+Tensor stream_pad_edge(const Tensor& x, int64_t Hp, int64_t Wp) {
+  check_operand(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0 && Hp >= x.size(2) && Wp >= x.size(3),
+              "imgcomp_stream: pad_edge takes a contiguous (N, C, h, w) tensor and a padded size >= (h, w), got ",
+              x.sizes(), " -> ", Hp, " x ", Wp);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({x.size(0), x.size(1), Hp, Wp}, x.options());
+  check_rc(ic_pad_edge(x.data_ptr<float>(), (int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)Hp,
+                       (int)Wp, y.data_ptr<float>(), stream_of(x)),
+           "pad_edge");
+  return y;
+}
+
+Tensor stream_crop_clamp(const Tensor& x, int64_t h, int64_t w) {
+  check_operand(x, "x");
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0 && h >= 1 && w >= 1 && h <= x.size(2) && w <= x.size(3),
+              "imgcomp_stream: crop_clamp takes (N, C, H, W) and a crop 1 <= (h, w) <= (H, W), got ", x.sizes(), " -> ",
+              h, " x ", w);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
+  const ic_act ax = act_of(x);
+  check_rc(ic_crop_clamp(&ax, (int)h, (int)w, y.data_ptr<float>(), stream_of(x)), "crop_clamp");
+  return y;
+}
+
+std::tuple<Tensor, std::vector<int64_t>> stream_symbolize_seg_meta(const Tensor& x, int64_t nseg) {
+  return {at::empty({x.numel()}, x.options().dtype(at::kInt)), std::vector<int64_t>((size_t)std::max<int64_t>(nseg, 0), 0)};
+}
+Tensor stream_encode_seg_meta(const Tensor& sym, int64_t nseg, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t,
+                              at::IntArrayRef, at::IntArrayRef, int64_t steps) {
+  TORCH_CHECK(nseg >= 1 && sym.numel() % nseg == 0, "imgcomp_stream: symbols do not make equal segments");
+  const size_t ob = ic_codec_compact_seg_bytes((int)nseg, sym.numel() / nseg, (int)steps);
+  TORCH_CHECK(ob > 0, "imgcomp_stream: bad symbol count or steps_per_chunk");
+  return at::empty({(int64_t)ob}, sym.options().dtype(at::kByte));
+}
+Tensor stream_decode_seg_meta(const Tensor& packed, int64_t nseg, int64_t seg_len, const std::optional<Tensor>&, int64_t,
+                              const Tensor&, int64_t, at::IntArrayRef, at::IntArrayRef, int64_t) {
+  return at::empty({nseg * seg_len}, packed.options().dtype(at::kFloat));
+}
+Tensor stream_pad_edge_meta(const Tensor& x, int64_t Hp, int64_t Wp) {
+  TORCH_CHECK(x.dim() == 4, "imgcomp_stream: pad_edge takes (N, C, h, w)");
+  return at::empty({x.size(0), x.size(1), Hp, Wp}, x.options());
+}
+Tensor stream_crop_clamp_meta(const Tensor& x, int64_t h, int64_t w) {
+  TORCH_CHECK(x.dim() == 4, "imgcomp_stream: crop_clamp takes (N, C, H, W)");
+  return at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1441,4 +1577,31 @@ TORCH_LIBRARY_IMPL(imgcomp_codec, Meta, m) {
   m.impl("build_tables", codec_build_tables_meta);
   m.impl("encode", codec_encode_meta);
   m.impl("decode", codec_decode_meta);
+}
+
+// The per-image streams' ops (compress_each / decompress_each): additive, in a namespace of their own.
+TORCH_LIBRARY(imgcomp_stream, m) {
+  m.def("symbolize_seg(Tensor x, int nseg) -> (Tensor, int[])");
+  m.def("encode_seg(Tensor sym, int nseg, Tensor? rows, int channels, Tensor pool, int nrows, int[] seg_k, "
+        "int[] seg_off, int steps_per_chunk) -> Tensor");
+  m.def("decode_seg(Tensor packed, int nseg, int seg_len, Tensor? rows, int channels, Tensor pool, int nrows, "
+        "int[] seg_k, int[] seg_off, int steps_per_chunk) -> Tensor");
+  m.def("pad_edge(Tensor x, int height, int width) -> Tensor");
+  m.def("crop_clamp(Tensor x, int height, int width) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_stream, CUDA, m) {
+  m.impl("symbolize_seg", stream_symbolize_seg);
+  m.impl("encode_seg", stream_encode_seg);
+  m.impl("decode_seg", stream_decode_seg);
+  m.impl("pad_edge", stream_pad_edge);
+  m.impl("crop_clamp", stream_crop_clamp);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_stream, Meta, m) {
+  m.impl("symbolize_seg", stream_symbolize_seg_meta);
+  m.impl("encode_seg", stream_encode_seg_meta);
+  m.impl("decode_seg", stream_decode_seg_meta);
+  m.impl("pad_edge", stream_pad_edge_meta);
+  m.impl("crop_clamp", stream_crop_clamp_meta);
 }

@@ -128,6 +128,43 @@ def _decode(payload, lengths, n, rows, channels, tables, steps, device):
     return _lib.codec_ops().decode(buf, int(n), rows, int(channels), tables, int(steps))
 
 
+# ---- segmented pieces (per-image streams): the images of a call lie back to back in one symbol buffer,
+# each with its own K and table, and one launch serves them all
+def symbolize_seg(x):
+    """x (N, C, *) -> (int32 symbols of the N images back to back, each in (*, c) order, [kmax of image n]).
+    ValueError naming the image whose symbols exceed the coder's limit."""
+    _lib.require_device(x)
+    sym, kmax = _lib.stream_ops().symbolize_seg(_to_last(x), int(x.shape[0]))
+    return sym, [int(k) for k in kmax]
+
+
+def table_pool(tables_of, kmaxes):
+    """(pool, rows, K per segment, table word offset per segment): one table per distinct K, built by
+    `tables_of(K)`, back to back in one device buffer; segments with the same K share theirs."""
+    offs, parts, at = {}, [], 0
+    for K in sorted(set(kmaxes)):
+        t = tables_of(K)
+        offs[K], rows = at, t.shape[0]
+        parts.append(t.reshape(-1))
+        at += t.numel()
+    pool = parts[0] if len(parts) == 1 else torch.cat(parts)
+    return pool, rows, [int(k) for k in kmaxes], [offs[k] for k in kmaxes]
+
+
+def _encode_seg(sym, nseg, rows, channels, tables_of, kmaxes, steps):
+    pool, nrows, ks, offs = table_pool(tables_of, kmaxes)
+    packed = _lib.stream_ops().encode_seg(sym, int(nseg), rows, int(channels), pool, nrows, ks, offs, int(steps))
+    parts = _codec.split_packed_seg(packed.cpu().numpy(), nseg, sym.numel() // nseg, steps)  # the one D2H copy
+    return [(payload, lens) for lens, payload in parts]
+
+
+def _decode_seg(payloads, lengths, seg_len, rows, channels, tables_of, kmaxes, steps, device):
+    pool, nrows, ks, offs = table_pool(tables_of, kmaxes)
+    buf = torch.from_numpy(_codec.join_packed_seg(list(zip(lengths, payloads))).copy()).to(device)
+    return _lib.stream_ops().decode_seg(buf, len(payloads), int(seg_len), rows, int(channels), pool, nrows, ks, offs,
+                                        int(steps))
+
+
 def _ref_layout(p):
     """The reference re-permutes the CDF output with the forward permutation
     instead of its inverse (entropy_model.py:108-113): for (N, C, H, W) the
@@ -190,6 +227,19 @@ class EntropyModel(BaseEntropyModel):
         flat = _decode(payload, lengths, n, None, self.channels, tables, steps_per_chunk, tables.device)
         return symbols_as_tensor(flat, tuple(shape))
 
+    def encode_symbols_seg(self, sym, kmaxes, steps_per_chunk=1024):
+        """Symbols of len(kmaxes) images back to back -> [(payload bytes, chunk lengths)] per image."""
+        return _encode_seg(sym, len(kmaxes), None, self.channels, self.tables, kmaxes, steps_per_chunk)
+
+    @torch.no_grad()
+    def decompress_seg(self, payloads, shape, lengths, kmaxes, steps_per_chunk=1024):
+        """M streams of images of one `shape` (1, C, *) -> the float tensor of integers (M, C, *)."""
+        self._codable()
+        dev = self._cdf_estimator.layers[0].weight.device
+        flat = _decode_seg(payloads, lengths, math.prod(shape), None, self.channels, self.tables, kmaxes,
+                           steps_per_chunk, dev)
+        return symbols_as_tensor(flat, (len(payloads), *shape[1:]))
+
 
 class SymmetricConditionalModel(BaseEntropyModel):
     """entropy_model.py:272-352; subclasses pick the standardized CDF."""
@@ -237,6 +287,19 @@ class SymmetricConditionalModel(BaseEntropyModel):
         tables = self.tables(kmax, sigma.device)
         flat = _decode(payload, lengths, sigma.numel(), self.scale_rows(sigma), 0, tables, steps_per_chunk,
                        sigma.device)
+        return symbols_as_tensor(flat, tuple(sigma.shape))
+
+    def encode_symbols_seg(self, sym, kmaxes, sigma, steps_per_chunk=1024):
+        """Symbols of the N = len(kmaxes) images of sigma (N, C, *) back to back -> [(payload, lengths)]."""
+        return _encode_seg(sym, len(kmaxes), self.scale_rows(sigma), 0, lambda K: self.tables(K, sigma.device), kmaxes,
+                           steps_per_chunk)
+
+    @torch.no_grad()
+    def decompress_seg(self, payloads, sigma, lengths, kmaxes, steps_per_chunk=1024):
+        """M streams coded with the M images of sigma (M, C, *) -> the float tensor of integers like sigma."""
+        self._codable()
+        flat = _decode_seg(payloads, lengths, sigma[0].numel(), self.scale_rows(sigma), 0,
+                           lambda K: self.tables(K, sigma.device), kmaxes, steps_per_chunk, sigma.device)
         return symbols_as_tensor(flat, tuple(sigma.shape))
 
     def quantize(self, x):

@@ -13,7 +13,7 @@ from ... import _lib
 from ... import codec as _codec
 from ... import noise as _noise
 from ...functional import AbsFn, NonNegMultiFn, route_weight_gradients
-from ..blocks.entropy_model import symbolize, symbols_as_tensor
+from ..blocks.entropy_model import symbolize, symbolize_seg, symbols_as_tensor
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
@@ -253,3 +253,92 @@ class Compressor2018(nn.Module):
         y_hat = cm.decompress(py, sigma, ly, h.kmax_y, h.R)
         x_hat = self.synthesis_transform(y_hat)
         return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)
+
+    # ---- per-image streams: any image size, every image its own self-contained stream (container
+    # "ICRP", codec.py).  The one rule that makes stream n decodable alone: h_s runs one image at a
+    # time on both sides, so the sigma bits that select the table rows do not depend on the batch.
+    def _codable_each(self):
+        self._codable()
+        self.entropy_model._codable()       # BIN == 1, before anything is computed
+        self.conditional_model._codable()
+
+    def _sigma_each(self, z_hat):
+        """h_s of every image of z_hat on its own (batch shape 1), concatenated."""
+        sig = [self.prior_synthesis(z_hat[n:n + 1]) for n in range(z_hat.shape[0])]
+        return sig[0] if len(sig) == 1 else torch.cat(sig)
+
+    @torch.no_grad()
+    def compress_each(self, x, steps_per_chunk=1024):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> a list of N bytes objects, one stream per image."""
+        self._codable_each()
+        if x.dim() != 4 or min(x.shape) < 1:
+            raise ValueError(f"compress_each: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
+        em, cm = self.entropy_model, self.conditional_model
+        N, _, h, w = x.shape
+        H, W = _codec.padded_size(h, w)
+        if (H, W) != (h, w):
+            _lib.require_device(x)
+            x = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(AbsFn.apply(y))
+        try:
+            z_sym, kz = symbolize_seg(z)
+            y_sym, ky = symbolize_seg(y)
+        except ValueError as e:
+            raise ValueError(f"compress_each: {e}") from None
+        # sigma from the integers the decoder will hold, one image at a time as the decoder computes it
+        sigma = self._sigma_each(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
+        sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
+        sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), steps_per_chunk)
+        out = []
+        for n in range(N):
+            hd = _codec.ImageHeader(1, H, W, y.shape[1], z.shape[1], cm.KIND, getattr(self, "compute_dtype", "fp32"),
+                                    int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max,
+                                    int(steps_per_chunk), kz[n], ky[n], h, w)
+            if tuple(z.shape[1:]) != hd.z_shape[1:] or tuple(y.shape[1:]) != hd.y_shape[1:]:
+                raise ValueError(f"compress_each: latents {tuple(y.shape)} / {tuple(z.shape)} are not the padded image "
+                                 f"size over {_codec.Y_DOWN} / {_codec.Z_DOWN}")
+            out.append(_codec.pack_image(hd, sz[n][1], sy[n][1], sz[n][0], sy[n][0]))
+        return out
+
+    @torch.no_grad()
+    def decompress_each(self, streams):
+        """A list of M bytes objects from `compress_each` (any sizes, coded in any calls; same weights, build,
+        COMPUTE_DTYPE and device type) -> a list of M tensors (1, 3, h_m, w_m).  Streams that share a padded
+        size and chunk size are decoded by the same launches and pass g_s as one batch."""
+        self._codable_each()
+        em, cm = self.entropy_model, self.conditional_model
+        abi, dt = int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32")
+        parsed = [_codec.parse_image(d, abi, dt) for d in streams]   # everything is validated before any launch
+        groups = {}
+        for m, (h, *_rest) in enumerate(parsed):
+            if h.kind != cm.KIND or h.hyper_channels != em.channels:
+                raise ValueError(f"decompress_each: stream {m} was coded by a different model (conditional kind / "
+                                 "channels)")
+            if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
+                raise ValueError(f"decompress_each: stream {m} was coded with a different scale table")
+            groups.setdefault((h.H, h.W, h.latent_channels, h.R), []).append(m)
+        out = [None] * len(parsed)
+        for (H, W, _cy, R), idx in groups.items():
+            hs = [parsed[m][0] for m in idx]
+            z_hat = em.decompress_seg([parsed[m][3] for m in idx], hs[0].z_shape, [parsed[m][1] for m in idx],
+                                      [h.kmax_z for h in hs], R)
+            sigma = self._sigma_each(z_hat)
+            if tuple(sigma.shape[1:]) != hs[0].y_shape[1:]:
+                raise ValueError(f"decompress_each: the model's sigma {tuple(sigma.shape)} is not the streams' latent "
+                                 f"shape {hs[0].y_shape}")
+            y_hat = cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
+                                      [h.kmax_y for h in hs], R)
+            x_hat = self.synthesis_transform(y_hat)
+            sizes = {(h.height, h.width) for h in hs}
+            if sizes == {(H, W)}:
+                x_hat = LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.).contiguous()
+                imgs = [x_hat[k:k + 1] for k in range(len(idx))]
+            elif len(sizes) == 1:
+                x_hat = _lib.stream_ops().crop_clamp(x_hat, *next(iter(sizes)))
+                imgs = [x_hat[k:k + 1] for k in range(len(idx))]
+            else:
+                imgs = [_lib.stream_ops().crop_clamp(x_hat[k:k + 1], h.height, h.width) for k, h in enumerate(hs)]
+            for m, img in zip(idx, imgs):
+                out[m] = img
+        return out

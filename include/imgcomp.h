@@ -504,6 +504,44 @@ int ic_codec_compact(const void* ws, const unsigned int* lengths, long long n, i
 int ic_codec_decode(const void* in, size_t in_bytes, long long n, const unsigned char* rows, int C,
                     const unsigned int* cdf, int nrows, int K, int steps_per_chunk, float* out, void* stream);
 
+/* ---- segmented entropy coder (per-image streams; additive to version 4).  nseg segments (images) of
+ *      seg_len symbols each lie back to back; segment s has its own K = seg_k[s] and its own table
+ *      [nrows][2 seg_k[s] + 2] at word offset seg_off[s] of `pool` (device, pool_words uint32 long; segments
+ *      with the same K may share a table).  seg_k / seg_off are host arrays, checked before any launch and
+ *      then copied as (K, offset) pairs into seg_dev (device, 2 * nseg ints).  Chunks never straddle a
+ *      segment: each has ceil(seg_len / (64 * steps_per_chunk)) chunks, the last possibly short, and the
+ *      bytes of segment s are exactly what ic_codec_encode writes for its symbols alone.  Row of symbol g
+ *      (index over all segments): rows[g], or g % C where rows is NULL (then seg_len % C must be 0). ---- */
+long long ic_codec_seg_chunks(int nseg, long long seg_len, int steps_per_chunk);      /* nseg * chunks per segment; 0: bad arguments */
+size_t ic_codec_encode_seg_ws(int nseg, long long seg_len, int steps_per_chunk);      /* chunks * (2 * 64 * steps_per_chunk + 256) bytes */
+size_t ic_codec_compact_seg_bytes(int nseg, long long seg_len, int steps_per_chunk);  /* 4 * chunks + the encode workspace */
+/* sym = rint(x) and kmax_dev[s] = max |sym| of segment s (device, nseg ints; integer atomic maximum); one
+ * copy of the nseg maxima to kmax_host and one wait for the stream.  IC_ERR_ARG (with kmax_host filled)
+ * when any exceeds IC_CODEC_KMAX. */
+int ic_codec_symbolize_seg(const float* x, int nseg, long long seg_len, int* sym, int* kmax_dev, int* kmax_host,
+                           void* stream);
+/* One wavefront per chunk over all nseg * chunks-per-segment chunks, (segment, chunk) order; a block stages
+ * its own segment's table in LDS when nrows * (2K + 2) * 4 <= 48 KiB and reads it from `pool` otherwise. */
+int ic_codec_encode_seg(const int* sym, int nseg, long long seg_len, const unsigned char* rows, int C,
+                        const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                        const long long* seg_off, int* seg_dev, int steps_per_chunk, void* ws, size_t ws_bytes,
+                        unsigned int* lengths, void* stream);
+/* ic_codec_compact for an explicit chunk count: out = [all chunk lengths][all chunk bytes] */
+int ic_codec_compact_seg(const void* ws, const unsigned int* lengths, long long chunks, int steps_per_chunk, void* out,
+                         size_t out_bytes, void* stream);
+/* in = [the segments' chunk lengths, (segment, chunk) order][their chunk bytes, same order]: the streams of
+ * nseg images of one tensor kind, concatenated.  The guarantees of ic_codec_decode hold per segment: any
+ * bytes decode to some symbols in [-seg_k[s], seg_k[s]]. */
+int ic_codec_decode_seg(const void* in, size_t in_bytes, int nseg, long long seg_len, const unsigned char* rows, int C,
+                        const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                        const long long* seg_off, int* seg_dev, int steps_per_chunk, float* out, void* stream);
+
+/* ---- image borders of the per-image streams.  ic_pad_edge: x (N, C, h, w) dense NCHW -> y (N, C, Hp, Wp)
+ *      dense NCHW, y[n,c,i,j] = x[n,c,min(i,h-1),min(j,w-1)].  ic_crop_clamp: x (any strides) -> y (N, C, h, w)
+ *      dense NCHW, y = max(min(x, 1), 0) on the top-left h x w: ic_bound_fwd upper 1 then lower 0, cropped. ---- */
+int ic_pad_edge(const float* x, int N, int C, int h, int w, int Hp, int Wp, float* y, void* stream);
+int ic_crop_clamp(const ic_act* x, int h, int w, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
