@@ -202,6 +202,11 @@ SIGNATURES = {
                                     P(c_ll), c_void, c_int, c_void, c_void]),
     "ic_pad_edge": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
     "ic_crop_clamp": (c_int, [_ACT, c_int, c_int, c_void, c_void]),
+    # mean-scale hyperprior: symbols and reconstruction about a mean (additive to ic_version 4)
+    "ic_codec_symbolize_mean": (c_int, [c_void, c_void, c_ll, c_void, c_void, P(c_int), c_void]),
+    "ic_codec_symbolize_mean_seg": (c_int, [c_void, c_void, c_int, c_ll, c_void, c_void, P(c_int), c_void]),
+    "ic_center_round": (c_int, [c_void, c_void, c_ll, c_void, c_void, c_void]),
+    "ic_add_mean": (c_int, [c_void, c_void, c_ll, c_void, c_void]),
 }
 
 _lib = None
@@ -224,6 +229,12 @@ def stream_ops():
     """torch.ops.imgcomp_stream (the segmented coder and the image borders of the per-image streams)."""
     ops()
     return torch.ops.imgcomp_stream
+
+
+def mean_ops():
+    """torch.ops.imgcomp_mean (the mean-scale hyperprior's symbolizers, quantiser and reconstruction)."""
+    ops()
+    return torch.ops.imgcomp_mean
 
 
 def ops():

@@ -1,5 +1,6 @@
-"""The compressed container of `Compressor2018.compress` / `decompress`, and the specification of
-the rANS bitstream inside it (kernels: csrc/codec.hip, `ic_codec_*`).  Host code only: nothing
+"""The compressed container of `Compressor2018.compress` / `decompress` (and of
+`MeanScaleCompressor2018`'s), and the specification of the rANS bitstream inside it (kernels:
+csrc/codec.hip and csrc/meancodec.hip, `ic_codec_*`).  Host code only: nothing
 here launches a kernel, and `parse` validates a buffer completely before the caller launches any.
 
 Bitstream of one tensor
@@ -7,6 +8,11 @@ Bitstream of one tensor
 Symbols.  The tensor's eval-mode quantization q = rint(x) as integers, flattened in (n, h, w, c)
 order (channel fastest).  K = kmax = max |q| of the tensor, K <= 2047; symbol index j = q + K in
 [0, 2K].
+With the mean-scale hyperprior (conditional kind 2 or 3 below) the symbols of y are those of the residual,
+q = rint(y - mu) with y - mu one float32 subtraction, where (mu, sigma) = h_s(z_hat) are computed from the decoded
+integers of z; K is the largest |residual|, and the decoder's reconstruction is y_hat = q + mu, one float32
+addition.  The symbols of z, the tables, the rows, the chunks and the payload are unchanged: the rows of y are pmfs
+at mean 0, which is what the residual is coded under.
 
 Tables.  A table has `rows` rows of 2K+2 unsigned cumulative counts: cdf[0] = 0 < cdf[1] < ... <
 cdf[2K+1] = 65536.  Symbol j has start = cdf[j], freq = cdf[j+1] - cdf[j] >= 1.  The row of symbol
@@ -49,7 +55,8 @@ Payload.  The chunks back to back, in order; the chunk lengths are kept beside i
 Container (little endian), one call = one batch = one bytes object
 -------------------------------------------------------------------
     magic "ICRA", u16 format version (1), u8 arithmetic tag (index of COMPUTE_DTYPE in
-    COMPUTE_DTYPES), u8 conditional kind (0 Laplace, 1 Gauss), u32 ABI version (ic_version()),
+    COMPUTE_DTYPES), u8 conditional kind (bit 0: 0 Laplace, 1 Gauss; bit 1 set: y is coded about a mean
+    from h_s, the mean-scale hyperprior; so 0..3, anything else is rejected), u32 ABI version (ic_version()),
     u32 N, H, W (image batch), u32 latent channels (y), u32 hyper channels (z),
     u32 L, f64 scale_min, f64 scale_max, u32 R, u32 kmax_z, u32 kmax_y,
     u64 symbols of z, u64 symbols of y, u32 chunks of z, u32 chunks of y,
@@ -65,7 +72,7 @@ reconstruction.  The two bitstreams are exactly the ones above for a batch of on
 image only in (h, w, c) order, K = the largest |symbol| of this image's tensor, chunks cut from the
 image's first symbol (no chunk holds symbols of two images), and the rows of y from
 sigma = h_s(z_hat) evaluated on this image alone (batch shape 1), whoever else is coded or decoded in
-the same call.
+the same call (with kind 2 or 3, mu comes from the same single-image evaluation).
     magic "ICRP", u16 format version (1), then the fields of the "ICRA" header from the arithmetic
     tag to the chunk counts, with N = 1 and H, W the padded size,
     u32 image height h, u32 image width w   (1 <= h <= H, H - h < 64; 1 <= w <= W, W - w < 64),
@@ -82,6 +89,7 @@ FORMAT_VERSION = 1
 KMAX_LIMIT = 2047          # IC_CODEC_KMAX: 2K+1 <= 4095 counts of >= 1 inside a 16-bit total
 MAX_SCALES = 256           # IC_CODEC_MAXL: rows are uint8
 MAX_STEPS = 65536          # IC_CODEC_MAXR
+KIND_MEAN = 2              # bit 1 of the conditional kind: y coded about a mean from h_s
 PRECISION = 16
 CHUNK_HEAD = 256           # 64 lanes x 4 bytes of state
 COMPUTE_DTYPES = ("fp32_split", "fp32", "bf16")
@@ -162,7 +170,7 @@ def fixed_bytes(h):
 def _check_header(h):
     if h.compute_dtype not in COMPUTE_DTYPES:
         raise ValueError(f"codec: unknown COMPUTE_DTYPE {h.compute_dtype!r}")
-    if h.kind not in (0, 1):
+    if h.kind not in (0, 1, 2, 3):
         raise ValueError(f"codec: unknown conditional kind {h.kind}")
     if min(h.N, h.H, h.W, h.latent_channels, h.hyper_channels) < 1:
         raise ValueError("codec: empty batch shape")

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "common.h"
+#include "codec_sym.h"
 #include "../../include/imgcomp.h"
 
 namespace {
@@ -28,24 +29,7 @@ constexpr size_t CODEC_LDS_BYTES = 49152;            // tables up to this size a
 // ------------------------------------------------------------------ symbolize
 // q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and max|q| by one
 // integer atomic per block (integer max is order-independent: deterministic).
-__device__ __forceinline__ int symbol_of(float v) {
-  // |q| beyond 2^30 (or NaN) only has to be reported as too large, not represented
-  const float q = fminf(fmaxf(rintf(v), -1073741824.f), 1073741824.f);
-  return (q == q) ? (int)q : 1073741824;
-}
-
-// the block's maximum of m, in thread 0
-__device__ __forceinline__ int block_max(int m) {
-  __shared__ int smax[16];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) m = max(m, __shfl_xor(m, o, 64));
-  if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = m;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) m = max(m, smax[w]);
-  return m;
-}
-
+// (symbol_of and block_max: codec_sym.h, shared with the mean-scale symbolizers of meancodec.hip)
 __global__ void codec_symbolize_k(const float* __restrict__ x, long long n, int* __restrict__ sym,
                                   int* __restrict__ kmax) {
   int m = 0;

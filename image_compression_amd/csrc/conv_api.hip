@@ -502,6 +502,8 @@ size_t need_or_zero(int rc, size_t n) { return rc ? 0 : n; }
 extern "C" {
 
 // 3: ic_fact_net / ic_fact_net_grads hold IC_FACT_NET_MAXL layers (round 6); 4: the entropy coder (ic_codec_*)
+// additive to 4 (no number of its own): the segmented coder and image borders, and the mean-scale ops
+// (ic_codec_symbolize_mean*, ic_center_round, ic_add_mean)
 int ic_version(void) { return 4; }
 
 int ic_conv_plan(int op, const ic_act* a, const ic_act* b, int k, int stride, int pad, int math, ic_plan* out) {

@@ -1375,6 +1375,86 @@ Tensor stream_crop_clamp_meta(const Tensor& x, int64_t h, int64_t w) {
   return at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
 }
 
+// ---------------------------------------------------------------- mean-scale hyperprior (imgcomp_mean)
+// y is coded about a mean: both operands are contiguous (the channels-last storage the coder flattens), of the
+// same element count in the same order; the outputs are flat, like the symbolizers' above.
+void check_mean_pair(const Tensor& a, const Tensor& mu, const char* what) {
+  check_operand(a, what);
+  check_operand(mu, "mu");
+  TORCH_CHECK(a.is_contiguous() && mu.is_contiguous(), "imgcomp_mean: ", what, " and mu must be contiguous");
+  TORCH_CHECK(a.numel() > 0 && a.numel() == mu.numel() && a.device() == mu.device(), "imgcomp_mean: ", what, " (",
+              a.numel(), " values) and mu (", mu.numel(), ") must hold the same number of values on one device");
+}
+
+std::tuple<Tensor, int64_t> mean_symbolize(const Tensor& y, const Tensor& mu) {
+  check_mean_pair(y, mu, "y");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor sym = at::empty({y.numel()}, y.options().dtype(at::kInt));
+  Tensor kd = at::empty({1}, y.options().dtype(at::kInt));
+  int kmax = 0;
+  const int rc = ic_codec_symbolize_mean(y.data_ptr<float>(), mu.data_ptr<float>(), y.numel(), sym.data_ptr<int>(),
+                                         kd.data_ptr<int>(), &kmax, stream_of(y));
+  TORCH_CHECK_VALUE(!(rc == IC_ERR_ARG && kmax > IC_CODEC_KMAX), "imgcomp_mean: a symbol of magnitude ", kmax,
+                    " exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "codec_symbolize_mean");
+  return {sym, (int64_t)kmax};
+}
+
+std::tuple<Tensor, std::vector<int64_t>> mean_symbolize_seg(const Tensor& y, const Tensor& mu, int64_t nseg) {
+  check_mean_pair(y, mu, "y");
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && y.numel() % nseg == 0, "imgcomp_mean: ", y.numel(), " values do not make ",
+              nseg, " equal segments");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor sym = at::empty({y.numel()}, y.options().dtype(at::kInt));
+  Tensor kd = at::empty({nseg}, y.options().dtype(at::kInt));
+  std::vector<int> kmax((size_t)nseg, 0);
+  const int rc = ic_codec_symbolize_mean_seg(y.data_ptr<float>(), mu.data_ptr<float>(), (int)nseg, y.numel() / nseg,
+                                             sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(y));
+  if (rc == IC_ERR_ARG)
+    for (int64_t s = 0; s < nseg; ++s)
+      TORCH_CHECK_VALUE(kmax[s] <= IC_CODEC_KMAX, "imgcomp_mean: image ", s, " has a symbol of magnitude ", kmax[s],
+                        ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "codec_symbolize_mean_seg");
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
+std::tuple<Tensor, Tensor> mean_center_round(const Tensor& y, const Tensor& mu) {
+  check_mean_pair(y, mu, "y");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor r = at::empty({y.numel()}, y.options());
+  Tensor y_hat = at::empty({y.numel()}, y.options());
+  check_rc(ic_center_round(y.data_ptr<float>(), mu.data_ptr<float>(), y.numel(), r.data_ptr<float>(),
+                           y_hat.data_ptr<float>(), stream_of(y)),
+           "center_round");
+  return {r, y_hat};
+}
+
+Tensor mean_add(const Tensor& r, const Tensor& mu) {
+  check_mean_pair(r, mu, "r");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(r.device());
+  Tensor y_hat = at::empty({r.numel()}, r.options());
+  check_rc(ic_add_mean(r.data_ptr<float>(), mu.data_ptr<float>(), r.numel(), y_hat.data_ptr<float>(), stream_of(r)),
+           "add_mean");
+  return y_hat;
+}
+
+std::tuple<Tensor, int64_t> mean_symbolize_meta(const Tensor& y, const Tensor& mu) {
+  TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
+  return {at::empty({y.numel()}, y.options().dtype(at::kInt)), 0};
+}
+std::tuple<Tensor, std::vector<int64_t>> mean_symbolize_seg_meta(const Tensor& y, const Tensor& mu, int64_t nseg) {
+  TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
+  return {at::empty({y.numel()}, y.options().dtype(at::kInt)), std::vector<int64_t>((size_t)std::max<int64_t>(nseg, 0), 0)};
+}
+std::tuple<Tensor, Tensor> mean_center_round_meta(const Tensor& y, const Tensor& mu) {
+  TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
+  return {at::empty({y.numel()}, y.options()), at::empty({y.numel()}, y.options())};
+}
+Tensor mean_add_meta(const Tensor& r, const Tensor& mu) {
+  TORCH_CHECK(r.numel() == mu.numel(), "imgcomp_mean: r and mu must hold the same number of values");
+  return at::empty({r.numel()}, r.options());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1604,4 +1684,26 @@ TORCH_LIBRARY_IMPL(imgcomp_stream, Meta, m) {
   m.impl("decode_seg", stream_decode_seg_meta);
   m.impl("pad_edge", stream_pad_edge_meta);
   m.impl("crop_clamp", stream_crop_clamp_meta);
+}
+
+// The mean-scale hyperprior's ops (MeanScaleCompressor2018): additive, in a namespace of their own.
+TORCH_LIBRARY(imgcomp_mean, m) {
+  m.def("symbolize(Tensor y, Tensor mu) -> (Tensor, int)");
+  m.def("symbolize_seg(Tensor y, Tensor mu, int nseg) -> (Tensor, int[])");
+  m.def("center_round(Tensor y, Tensor mu) -> (Tensor, Tensor)");
+  m.def("add_mean(Tensor r, Tensor mu) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_mean, CUDA, m) {
+  m.impl("symbolize", mean_symbolize);
+  m.impl("symbolize_seg", mean_symbolize_seg);
+  m.impl("center_round", mean_center_round);
+  m.impl("add_mean", mean_add);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_mean, Meta, m) {
+  m.impl("symbolize", mean_symbolize_meta);
+  m.impl("symbolize_seg", mean_symbolize_seg_meta);
+  m.impl("center_round", mean_center_round_meta);
+  m.impl("add_mean", mean_add_meta);
 }

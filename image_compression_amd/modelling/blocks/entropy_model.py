@@ -111,6 +111,41 @@ def symbolize(x):
     return sym, int(kmax)
 
 
+def _mean_last(x, mean):
+    """(x, mean) as dense channels-last storage; the mean must have x's shape (its elements pair with x's)."""
+    _lib.require_device(x, mean)
+    if tuple(mean.shape) != tuple(x.shape):
+        raise ValueError(f"the mean {tuple(mean.shape)} must have the shape of the tensor it centres {tuple(x.shape)}")
+    return _to_last(x), _to_last(mean)
+
+
+def symbolize_mean(y, mean):
+    """`symbolize` of the residual: int32 rint(y - mean), one fp32 subtraction per element, and its kmax."""
+    sym, kmax = _lib.mean_ops().symbolize(*_mean_last(y, mean))
+    return sym, int(kmax)
+
+
+def symbolize_mean_seg(y, mean):
+    """`symbolize_seg` of the residual rint(y - mean): [kmax of image n]; ValueError naming the image."""
+    sym, kmax = _lib.mean_ops().symbolize_seg(*_mean_last(y, mean), int(y.shape[0]))
+    return sym, [int(k) for k in kmax]
+
+
+def center_round(y, mean):
+    """(r, y_hat) = (rint(y - mean), r + mean) as (N, C, *) tensors over channels-last storage: the eval-mode
+    quantiser about a mean.  Inference only (no autograd node)."""
+    yl, ml = _mean_last(y, mean)
+    r, y_hat = _lib.mean_ops().center_round(yl, ml)
+    return symbols_as_tensor(r, tuple(y.shape)), symbols_as_tensor(y_hat, tuple(y.shape))
+
+
+def add_mean(flat, mean):
+    """The decoder's y_hat = r + mean (the addition of `center_round`, bit for bit) from the flat float
+    integers r in (n, *, c) order, as the (N, C, *) tensor over that storage."""
+    _lib.require_device(flat, mean)
+    return symbols_as_tensor(_lib.mean_ops().add_mean(flat, _to_last(mean)), tuple(mean.shape))
+
+
 def symbols_as_tensor(flat, shape):
     """Float symbols flattened in (n, *, c) order -> the logical (N, C, *) tensor over that
     channels-last storage: the layout the eval forward's quantized tensors have."""
@@ -269,38 +304,54 @@ class SymmetricConditionalModel(BaseEntropyModel):
         _, mids = _codec.scale_table(self.num_scales, self.scale_min, self.scale_max)
         return _lib.codec_ops().scale_index(_to_last(sigma), [float(m) for m in mids])
 
-    def encode_symbols(self, sym, kmax, sigma, steps_per_chunk=1024):
+    # With `mean` (N, C, *) the symbols are those of the residual y - mean (mean-scale hyperprior): the tables,
+    # rows and chunks are the same, K is the largest |residual|, and the decoders return r + mean.
+    @staticmethod
+    def _check_mean(mean, sigma):
+        if mean is not None and tuple(mean.shape) != tuple(sigma.shape):
+            raise ValueError(f"the mean {tuple(mean.shape)} must have sigma's shape {tuple(sigma.shape)}")
+
+    def encode_symbols(self, sym, kmax, sigma, steps_per_chunk=1024, mean=None):
+        """`sym`: rint(y), or with `mean` rint(y - mean) (`symbolize_mean`); the mean itself is not coded."""
+        self._check_mean(mean, sigma)
         return _encode(sym, self.scale_rows(sigma), 0, self.tables(kmax, sigma.device), steps_per_chunk)
 
     @torch.no_grad()
-    def compress(self, y, sigma, steps_per_chunk=1024):
+    def compress(self, y, sigma, steps_per_chunk=1024, mean=None):
         """y, sigma (N, C, *) -> (payload bytes, chunk lengths uint32[chunks], kmax)."""
         self._codable()
-        sym, kmax = symbolize(y)
-        payload, lens = self.encode_symbols(sym, kmax, sigma.expand_as(y), steps_per_chunk)
+        sigma = sigma.expand_as(y)
+        sym, kmax = symbolize(y) if mean is None else symbolize_mean(y, mean.expand_as(y))
+        payload, lens = self.encode_symbols(sym, kmax, sigma, steps_per_chunk)
         return payload, lens, kmax
 
     @torch.no_grad()
-    def decompress(self, payload, sigma, lengths, kmax, steps_per_chunk=1024):
-        """The float tensor of integers, shaped like sigma, that `compress` coded with this sigma."""
+    def decompress(self, payload, sigma, lengths, kmax, steps_per_chunk=1024, mean=None):
+        """The float tensor of integers, shaped like sigma, that `compress` coded with this sigma; with `mean`,
+        those integers plus the mean."""
         self._codable()
+        self._check_mean(mean, sigma)
         tables = self.tables(kmax, sigma.device)
         flat = _decode(payload, lengths, sigma.numel(), self.scale_rows(sigma), 0, tables, steps_per_chunk,
                        sigma.device)
-        return symbols_as_tensor(flat, tuple(sigma.shape))
+        return symbols_as_tensor(flat, tuple(sigma.shape)) if mean is None else add_mean(flat, mean)
 
-    def encode_symbols_seg(self, sym, kmaxes, sigma, steps_per_chunk=1024):
-        """Symbols of the N = len(kmaxes) images of sigma (N, C, *) back to back -> [(payload, lengths)]."""
+    def encode_symbols_seg(self, sym, kmaxes, sigma, steps_per_chunk=1024, mean=None):
+        """Symbols of the N = len(kmaxes) images of sigma (N, C, *) back to back -> [(payload, lengths)];
+        `mean` as in `encode_symbols` (`symbolize_mean_seg`)."""
+        self._check_mean(mean, sigma)
         return _encode_seg(sym, len(kmaxes), self.scale_rows(sigma), 0, lambda K: self.tables(K, sigma.device), kmaxes,
                            steps_per_chunk)
 
     @torch.no_grad()
-    def decompress_seg(self, payloads, sigma, lengths, kmaxes, steps_per_chunk=1024):
-        """M streams coded with the M images of sigma (M, C, *) -> the float tensor of integers like sigma."""
+    def decompress_seg(self, payloads, sigma, lengths, kmaxes, steps_per_chunk=1024, mean=None):
+        """M streams coded with the M images of sigma (M, C, *) -> the float tensor of integers like sigma; with
+        `mean`, those integers plus the mean."""
         self._codable()
+        self._check_mean(mean, sigma)
         flat = _decode_seg(payloads, lengths, sigma[0].numel(), self.scale_rows(sigma), 0,
                            lambda K: self.tables(K, sigma.device), kmaxes, steps_per_chunk, sigma.device)
-        return symbols_as_tensor(flat, tuple(sigma.shape))
+        return symbols_as_tensor(flat, tuple(sigma.shape)) if mean is None else add_mean(flat, mean)
 
     def quantize(self, x):
         """_quantize on its own (train: noise, eval: round): with likelihood() the two halves of

@@ -28,3 +28,13 @@ class HyperpriorSynthesisTransform(nn.Module):
 
     def forward(self, x):
         return ExpClampFn.apply(self._layers(x), 1e-10, 1e10)
+
+    # forward(x) in two steps, for a model with a second head on the same trunk
+    # (MeanScaleCompressor2018): finish(trunk(x)) runs the modules forward(x) runs, in its order.
+    def trunk(self, x):
+        """The activation that feeds the last layer (every layer but the last, ReLU included)."""
+        return self._layers[:-1](x)
+
+    def finish(self, t):
+        """sigma from the trunk activation: the last layer, then the exp-clamp."""
+        return ExpClampFn.apply(self._layers[-1](t), 1e-10, 1e10)

@@ -13,7 +13,7 @@ from ... import _lib
 from ... import codec as _codec
 from ... import noise as _noise
 from ...functional import AbsFn, NonNegMultiFn, route_weight_gradients
-from ..blocks.entropy_model import symbolize, symbolize_seg, symbols_as_tensor
+from ..blocks.entropy_model import symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
@@ -187,6 +187,9 @@ class Compressor2018(nn.Module):
             x_tilde = self.synthesis_transform(y_tilde)
             x_tilde = LowerBound.apply(UpperBound.apply(x_tilde, 1.), 0.)
             dist = self.distortion_loss(x, x_tilde)
+        return x_tilde.detach(), self._losses(z_ce, y_ce, dist, num_pixels)
+
+    def _losses(self, z_ce, y_ce, dist, num_pixels):
         total_dist = sum(dist.values())
         entropy = (z_ce + y_ce) / num_pixels
         total = self.distortion_loss_weight * total_dist + entropy
@@ -197,7 +200,7 @@ class Compressor2018(nn.Module):
             "total_loss": total,
         }
         losses.update({k: v.detach() for k, v in dist.items()})
-        return x_tilde.detach(), losses
+        return losses
 
     def distortion_loss(self, img1, img2):
         return {name: fn(img1, img2) for name, fn in self.distortion_loss_fns.items()}
@@ -209,6 +212,18 @@ class Compressor2018(nn.Module):
             raise RuntimeError("compress / decompress run in eval mode only: call model.eval() first")
         self._clear_reparameterised()
 
+    # The three points where a model with another hyperprior differs (MeanScaleCompressor2018): what h_a
+    # reads, what h_s gives, and the conditional-kind byte that says so in the container.
+    def _hyper_input(self, y):
+        return AbsFn.apply(y)
+
+    def _prior(self, z_hat):
+        """(sigma, mean) from the hyper-latent's integers; mean None: y is coded about 0."""
+        return self.prior_synthesis(z_hat), None
+
+    def _stream_kind(self):
+        return self.conditional_model.KIND
+
     @torch.no_grad()
     def compress(self, x, steps_per_chunk=1024):
         """x (N, 3, H, W) in [0, 1], H and W multiples of 64 -> one bytes object for the batch."""
@@ -219,14 +234,14 @@ class Compressor2018(nn.Module):
         em, cm = self.entropy_model, self.conditional_model
         N, _, H, W = x.shape
         y = self.analysis_transform(x)
-        z = self.prior_analysis(AbsFn.apply(y))
+        z = self.prior_analysis(self._hyper_input(y))
         z_sym, kz = symbolize(z)
-        # sigma from the integers the decoder will hold, in the layout it will hold them in
-        sigma = self.prior_synthesis(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
+        # sigma (and the mean) from the integers the decoder will hold, in the layout it will hold them in
+        sigma, mean = self._prior(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
         pz, lz = em.encode_symbols(z_sym, kz, steps_per_chunk)
-        y_sym, ky = symbolize(y)
-        py, ly = cm.encode_symbols(y_sym, ky, sigma.expand_as(y), steps_per_chunk)
-        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], cm.KIND, getattr(self, "compute_dtype", "fp32"),
+        y_sym, ky = symbolize(y) if mean is None else symbolize_mean(y, mean)
+        py, ly = cm.encode_symbols(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)
+        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], self._stream_kind(), getattr(self, "compute_dtype", "fp32"),
                           int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max, int(steps_per_chunk),
                           kz, ky)
         if tuple(z.shape) != h.z_shape or tuple(y.shape) != h.y_shape:
@@ -241,16 +256,16 @@ class Compressor2018(nn.Module):
         self._codable()
         em, cm = self.entropy_model, self.conditional_model
         h, lz, ly, pz, py = _codec.parse(data, int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32"))
-        if h.kind != cm.KIND or h.hyper_channels != em.channels:
+        if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
             raise ValueError("decompress: the stream was coded by a different model (conditional kind / channels)")
         if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
             raise ValueError("decompress: the stream was coded with a different scale table")
         z_hat = em.decompress(pz, h.z_shape, lz, h.kmax_z, h.R)
-        sigma = self.prior_synthesis(z_hat)
+        sigma, mean = self._prior(z_hat)
         if tuple(sigma.shape) != h.y_shape:
             raise ValueError(f"decompress: the model's sigma {tuple(sigma.shape)} is not the stream's latent shape "
                              f"{h.y_shape}")
-        y_hat = cm.decompress(py, sigma, ly, h.kmax_y, h.R)
+        y_hat = cm.decompress(py, sigma, ly, h.kmax_y, h.R, mean=mean)
         x_hat = self.synthesis_transform(y_hat)
         return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)
 
@@ -262,10 +277,13 @@ class Compressor2018(nn.Module):
         self.entropy_model._codable()       # BIN == 1, before anything is computed
         self.conditional_model._codable()
 
-    def _sigma_each(self, z_hat):
-        """h_s of every image of z_hat on its own (batch shape 1), concatenated."""
-        sig = [self.prior_synthesis(z_hat[n:n + 1]) for n in range(z_hat.shape[0])]
-        return sig[0] if len(sig) == 1 else torch.cat(sig)
+    def _prior_each(self, z_hat):
+        """`_prior` of every image of z_hat on its own (batch shape 1), concatenated."""
+        parts = [self._prior(z_hat[n:n + 1]) for n in range(z_hat.shape[0])]
+        if len(parts) == 1:
+            return parts[0]
+        sigma, mean = zip(*parts)
+        return torch.cat(sigma), (None if mean[0] is None else torch.cat(mean))
 
     @torch.no_grad()
     def compress_each(self, x, steps_per_chunk=1024):
@@ -280,21 +298,22 @@ class Compressor2018(nn.Module):
             _lib.require_device(x)
             x = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
         y = self.analysis_transform(x)
-        z = self.prior_analysis(AbsFn.apply(y))
+        z = self.prior_analysis(self._hyper_input(y))
         try:
             z_sym, kz = symbolize_seg(z)
-            y_sym, ky = symbolize_seg(y)
+            # sigma (and the mean) from the integers the decoder will hold, one image at a time as the decoder
+            # computes them
+            sigma, mean = self._prior_each(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
+            y_sym, ky = symbolize_seg(y) if mean is None else symbolize_mean_seg(y, mean)
         except ValueError as e:
             raise ValueError(f"compress_each: {e}") from None
-        # sigma from the integers the decoder will hold, one image at a time as the decoder computes it
-        sigma = self._sigma_each(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
         sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
-        sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), steps_per_chunk)
+        sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)
         out = []
         for n in range(N):
-            hd = _codec.ImageHeader(1, H, W, y.shape[1], z.shape[1], cm.KIND, getattr(self, "compute_dtype", "fp32"),
-                                    int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max,
-                                    int(steps_per_chunk), kz[n], ky[n], h, w)
+            hd = _codec.ImageHeader(1, H, W, y.shape[1], z.shape[1], self._stream_kind(),
+                                    getattr(self, "compute_dtype", "fp32"), int(_lib.load().ic_version()), cm.num_scales,
+                                    cm.scale_min, cm.scale_max, int(steps_per_chunk), kz[n], ky[n], h, w)
             if tuple(z.shape[1:]) != hd.z_shape[1:] or tuple(y.shape[1:]) != hd.y_shape[1:]:
                 raise ValueError(f"compress_each: latents {tuple(y.shape)} / {tuple(z.shape)} are not the padded image "
                                  f"size over {_codec.Y_DOWN} / {_codec.Z_DOWN}")
@@ -312,7 +331,7 @@ class Compressor2018(nn.Module):
         parsed = [_codec.parse_image(d, abi, dt) for d in streams]   # everything is validated before any launch
         groups = {}
         for m, (h, *_rest) in enumerate(parsed):
-            if h.kind != cm.KIND or h.hyper_channels != em.channels:
+            if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
                 raise ValueError(f"decompress_each: stream {m} was coded by a different model (conditional kind / "
                                  "channels)")
             if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
@@ -323,12 +342,12 @@ class Compressor2018(nn.Module):
             hs = [parsed[m][0] for m in idx]
             z_hat = em.decompress_seg([parsed[m][3] for m in idx], hs[0].z_shape, [parsed[m][1] for m in idx],
                                       [h.kmax_z for h in hs], R)
-            sigma = self._sigma_each(z_hat)
+            sigma, mean = self._prior_each(z_hat)
             if tuple(sigma.shape[1:]) != hs[0].y_shape[1:]:
                 raise ValueError(f"decompress_each: the model's sigma {tuple(sigma.shape)} is not the streams' latent "
                                  f"shape {hs[0].y_shape}")
             y_hat = cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
-                                      [h.kmax_y for h in hs], R)
+                                      [h.kmax_y for h in hs], R, mean=mean)
             x_hat = self.synthesis_transform(y_hat)
             sizes = {(h.height, h.width) for h in hs}
             if sizes == {(H, W)}:

@@ -54,7 +54,9 @@ typedef struct ic_act {
 } ic_act;
 
 /* ---- library ---- */
-int ic_version(void);                 /* ABI version (monotonic; 3: ic_fact_net with IC_FACT_NET_MAXL layers; 4: ic_codec_*) */
+int ic_version(void);                 /* ABI version (monotonic; 3: ic_fact_net with IC_FACT_NET_MAXL layers; 4: ic_codec_*;
+                                         additive to 4: ic_codec_*_seg, ic_pad_edge / ic_crop_clamp, and the mean-scale ops
+                                         ic_codec_symbolize_mean*, ic_center_round, ic_add_mean) */
 int ic_device_sync_check(void* stream); /* hipStreamQuery-free no-op launch test */
 
 /* ---- Conv2d (k x k, stride, zero pad): y = conv(x, w) + b, act 0=none 1=relu
@@ -541,6 +543,22 @@ int ic_codec_decode_seg(const void* in, size_t in_bytes, int nseg, long long seg
  *      dense NCHW, y = max(min(x, 1), 0) on the top-left h x w: ic_bound_fwd upper 1 then lower 0, cropped. ---- */
 int ic_pad_edge(const float* x, int N, int C, int h, int w, int Hp, int Wp, float* y, void* stream);
 int ic_crop_clamp(const ic_act* x, int h, int w, float* y, void* stream);
+
+/* ---- mean-scale hyperprior (additive to version 4): y is coded about a mean mu = h_s(z_hat).  y and mu are
+ *      dense storage of the same n elements in the same order (the caller checks the counts).  d = y - mu is
+ *      one fp32 subtraction and y_hat = r + mu one fp32 addition, neither contracted with anything, so
+ *      ic_add_mean gives the bits ic_center_round gives for the same r and mu. ---- */
+/* ic_codec_symbolize with sym[i] = the symbol of y[i] - mu[i] (same clamp-and-NaN rule, same kmax contract) */
+int ic_codec_symbolize_mean(const float* y, const float* mu, long long n, int* sym, int* kmax_dev, int* kmax_host,
+                            void* stream);
+/* ic_codec_symbolize_seg likewise: kmax_dev[s] / kmax_host[s] = max |sym| of segment s */
+int ic_codec_symbolize_mean_seg(const float* y, const float* mu, int nseg, long long seg_len, int* sym, int* kmax_dev,
+                                int* kmax_host, void* stream);
+/* r[i] = rintf(y[i] - mu[i]) as the float the decoder will hold (a -0.0 is written as +0.0), y_hat[i] = r[i] + mu[i]:
+ * the eval-mode quantiser (r and y_hat distinct buffers) */
+int ic_center_round(const float* y, const float* mu, long long n, float* r, float* y_hat, void* stream);
+/* y_hat[i] = r[i] + mu[i]: the decoder's reconstruction from the float integers r it decoded */
+int ic_add_mean(const float* r, const float* mu, long long n, float* y_hat, void* stream);
 
 #ifdef __cplusplus
 }

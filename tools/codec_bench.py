@@ -7,6 +7,14 @@ symbols of the same image.  One JSON line; --out also writes it to a file.
 
     python tools/codec_bench.py [--reps 10] [--height 512] [--width 768] [--scale 1] [--out FILE]
     python tools/codec_bench.py --each 8 [--reps 10] [--scale 32] [--out profiles/codec_each_bench.json]
+    python tools/codec_bench.py --compare 8 [--reps 10] [--scale 32] [--out FILE]
+
+--arch NAME (default Compressor2018) runs the two modes above on another registered model, e.g.
+MeanScaleCompressor2018; the output then carries an "arch" key.
+
+--compare N times Compressor2018 and MeanScaleCompressor2018 alternately in one process: compress / decompress
+and compress_each / decompress_each at 1 and N images of --height x --width (ms per image, best of --reps), the
+mean-scale model's elementwise ops beside their scale-only counterparts by device events, and the coded bytes of both.
 
 --each N measures per-image streams instead: N images of --height x --width coded (a) by the loop of
 compress(x[n:n+1]) / decompress and (b) by compress_each / decompress_each, timed alternately in one process
@@ -56,7 +64,7 @@ def each_bench(args, model, cfg):
     """--each N: the loop over single-image batches against compress_each / decompress_each."""
     from image_compression_amd import _lib, codec
     from image_compression_amd import functional as F
-    from image_compression_amd.modelling.blocks.entropy_model import symbolize_seg, table_pool
+    from image_compression_amd.modelling.blocks.entropy_model import symbolize_mean_seg, symbolize_seg, table_pool
     N, H, W, reps = args.each, args.height, args.width, args.reps
     g = torch.Generator(device="cuda").manual_seed(5)
     x = torch.rand(N, 3, H, W, device="cuda", generator=g)
@@ -86,14 +94,22 @@ def each_bench(args, model, cfg):
         # the coder ops alone, on the latents of these images: N launches of the whole-tensor kernels against
         # one launch of the segmented ones
         y = model.analysis_transform(x)
-        z = model.prior_analysis(F.AbsFn.apply(y))
-        y_sym, ky = symbolize_seg(y)
+        z = model.prior_analysis(model._hyper_input(y))
         z_sym, kz = symbolize_seg(z)
         z_hat = z_sym.float().view(N, *z.shape[2:], z.shape[1]).movedim(-1, 1)
-        sigma = model._sigma_each(z_hat).expand_as(y)
+        sigma, mean = model._prior_each(z_hat)
+        sigma = sigma.expand_as(y)
+        y_sym, ky = symbolize_seg(y) if mean is None else symbolize_mean_seg(y, mean)
         rows = cm.scale_rows(sigma)
         ny, nz = y_sym.numel() // N, z_sym.numel() // N
         y_l = y.movedim(1, -1).contiguous()
+        if mean is None:
+            sym_loop = lambda: [ops.symbolize(y_l[n]) for n in range(N)]
+            sym_seg = lambda: sops.symbolize_seg(y_l, N)
+        else:
+            m_l, mops = mean.movedim(1, -1).contiguous(), _lib.mean_ops()
+            sym_loop = lambda: [mops.symbolize(y_l[n], m_l[n]) for n in range(N)]
+            sym_seg = lambda: mops.symbolize_seg(y_l, m_l, N)
         ty = {K: cm.tables(K, x.device) for K in set(ky)}
         tz = {K: em.tables(K) for K in set(kz)}
         pool_y, nrows_y, ks_y, offs_y = table_pool(lambda K: ty[K], ky)
@@ -103,8 +119,8 @@ def each_bench(args, model, cfg):
         buf_y = torch.from_numpy(codec.join_packed_seg(parts).copy()).cuda()
         one_y = [torch.from_numpy(codec.join_packed(l, p).copy()).cuda() for l, p in parts]
         kern = {
-            "symbolize_y_loop": _events(lambda: [ops.symbolize(y_l[n]) for n in range(N)], reps),
-            "symbolize_y_seg": _events(lambda: sops.symbolize_seg(y_l, N), reps),
+            "symbolize_y_loop": _events(sym_loop, reps),
+            "symbolize_y_seg": _events(sym_seg, reps),
             "encode_y_loop": _events(lambda: [ops.encode(y_sym[n * ny:(n + 1) * ny], rows[n * ny:(n + 1) * ny], 0,
                                                          ty[ky[n]], R) for n in range(N)], reps),
             "encode_y_seg": _events(lambda: sops.encode_seg(y_sym, N, rows, 0, pool_y, nrows_y, ks_y, offs_y, R), reps),
@@ -118,8 +134,8 @@ def each_bench(args, model, cfg):
                                     reps),
             "tables_y_loop": _events(lambda: [cm.tables(K, x.device) for K in ky], reps),
             "tables_y_seg": _events(lambda: table_pool(lambda K: cm.tables(K, x.device), ky), reps),
-            "h_s_single_x_n": _events(lambda: model._sigma_each(z_hat), reps),
-            "h_s_batched": _events(lambda: model.prior_synthesis(z_hat), reps),
+            "h_s_single_x_n": _events(lambda: model._prior_each(z_hat), reps),
+            "h_s_batched": _events(lambda: model._prior(z_hat), reps),
             "pad_edge_500x750": _events(lambda: sops.pad_edge(x_odd, 512, 768), reps),
             "crop_clamp_500x750": _events(lambda: sops.crop_clamp(want, 500, 750), reps),
         }
@@ -155,20 +171,20 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--each", type=int, default=0, metavar="N",
                     help="per-image streams: the loop of compress(x[n:n+1]) against compress_each over N images")
+    ap.add_argument("--arch", default="Compressor2018", help="the registered model to measure (META_ARCHITECTURE)")
+    ap.add_argument("--compare", type=int, default=0, metavar="N",
+                    help="Compressor2018 and MeanScaleCompressor2018 alternately, at 1 and N images")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
-    from image_compression_amd.modelling.blocks.entropy_model import symbolize
-    cfg = get_cfg_defaults()
-    cfg.MODEL.LOSS.REDUCTION = "mean"
-    torch.manual_seed(0)
-    model = modelling.build_model(cfg).cuda().eval()
-    if args.scale != 1.0:
-        last = [m for m in model.analysis_transform.modules() if hasattr(m, "weight") and m.weight.dim() == 4][-1]
-        with torch.no_grad():
-            last.weight.mul_(args.scale)
+    from image_compression_amd.modelling.blocks.entropy_model import symbolize, symbolize_mean
+    if args.compare:
+        _emit(compare_bench(args), args.out)
+        return
+    model, cfg = _build(args.arch, args.scale)
+    tag = lambda out: out if args.arch == "Compressor2018" else dict(out, arch=args.arch)
     if args.each:
-        _emit(each_bench(args, model, cfg), args.out)
+        _emit(tag(each_bench(args, model, cfg)), args.out)
         return
     x = torch.rand(1, 3, args.height, args.width, device="cuda", generator=torch.Generator(device="cuda").manual_seed(5))
     ops = _lib.codec_ops()
@@ -189,18 +205,23 @@ def main():
         # the coder's ops alone, on this image's latents
         h = codec.parse(data, int(_lib.load().ic_version()), cfg.MODEL.COMPUTE_DTYPE)[0]
         y = model.analysis_transform(x)
-        z = model.prior_analysis(F.AbsFn.apply(y))
+        z = model.prior_analysis(model._hyper_input(y))
         z_sym, kz = symbolize(z)
-        y_sym, ky = symbolize(y)
-        sigma = model.prior_synthesis(z_sym.float().view(1, *z.shape[2:], z.shape[1]).movedim(-1, 1)).expand_as(y)
+        sigma, mean = model._prior(z_sym.float().view(1, *z.shape[2:], z.shape[1]).movedim(-1, 1))
+        sigma = sigma.expand_as(y)
+        y_sym, ky = symbolize(y) if mean is None else symbolize_mean(y, mean)
         sig_l = sigma.movedim(1, -1).contiguous()
+        if mean is None:
+            sym_y = lambda: ops.symbolize(y.movedim(1, -1).contiguous())
+        else:
+            sym_y = lambda: _lib.mean_ops().symbolize(y.movedim(1, -1).contiguous(), mean.movedim(1, -1).contiguous())
         mids = [float(m) for m in codec.scale_table(cm.num_scales, cm.scale_min, cm.scale_max)[1]]
         tz, ty = em.tables(kz), cm.tables(ky, x.device)
         rows = ops.scale_index(sig_l, mids)
         pz, py = ops.encode(z_sym, None, em.channels, tz, h.R), ops.encode(y_sym, rows, 0, ty, h.R)
         nz, ny = codec.num_chunks(z_sym.numel(), h.R), codec.num_chunks(y_sym.numel(), h.R)
         kern = {
-            "symbolize_y": events(lambda: ops.symbolize(y.movedim(1, -1).contiguous())),
+            "symbolize_y": events(sym_y),
             "scale_index_y": events(lambda: ops.scale_index(sig_l, mids)),
             "tables_z": events(lambda: em.tables(kz)),
             "tables_y": events(lambda: cm.tables(ky, x.device)),
@@ -226,7 +247,79 @@ def main():
         "compute_dtype": cfg.MODEL.COMPUTE_DTYPE,
         "data": "synthetic uniform [0,1) image resident in HBM; random-init weights (reference init, seed 0)",
     }
-    _emit(out, args.out)
+    _emit(tag(out), args.out)
+
+
+def _build(arch, scale):
+    from image_compression_amd import get_cfg_defaults, modelling
+    cfg = get_cfg_defaults()
+    cfg.MODEL.LOSS.REDUCTION = "mean"
+    cfg.MODEL.META_ARCHITECTURE = arch
+    torch.manual_seed(0)
+    model = modelling.build_model(cfg).cuda().eval()
+    if scale != 1.0:
+        last = [m for m in model.analysis_transform.modules() if hasattr(m, "weight") and m.weight.dim() == 4][-1]
+        with torch.no_grad():
+            last.weight.mul_(scale)
+    return model, cfg
+
+
+def compare_bench(args):
+    """--compare N: the scale-only and the mean-scale model, one repetition of each at a time."""
+    from image_compression_amd import _lib
+    from image_compression_amd import functional as F
+    archs = ("Compressor2018", "MeanScaleCompressor2018")
+    models = {a: _build(a, args.scale)[0] for a in archs}
+    H, W, reps = args.height, args.width, args.reps
+    g = torch.Generator(device="cuda").manual_seed(5)
+    out = {"metric": f"scale-only and mean-scale codec, ms per image at 3 x {H} x {W}, weight cache, best of {reps} "
+                     "alternating reps", "unit": "ms per image", "weight_scale": args.scale, "reps": reps,
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0)"}
+    with torch.no_grad(), F.weight_cache():
+        for N in sorted({1, args.compare}):
+            x = torch.rand(N, 3, H, W, device="cuda", generator=g)
+            data, streams = {}, {}
+            for a, m in models.items():
+                for _ in range(2):                           # warm-up of every candidate
+                    data[a], streams[a] = m.compress(x), m.compress_each(x)
+                    same = bool(torch.equal(m.decompress(data[a]), m(x)[0]))
+                    m.decompress_each(streams[a])
+                out[f"{a}_decompress_equals_forward_n{N}"] = same
+            fns = {"compress": lambda m, a: m.compress(x), "decompress": lambda m, a: m.decompress(data[a]),
+                   "compress_each": lambda m, a: m.compress_each(x),
+                   "decompress_each": lambda m, a: m.decompress_each(streams[a])}
+            t = {(k, a): [] for k in fns for a in archs}
+            for _ in range(reps):
+                for k, fn in fns.items():
+                    for a, m in models.items():
+                        t[k, a].append(_wall(lambda: fn(m, a), 1))
+            for (k, a), v in t.items():
+                out[f"{a}_{k}_ms_n{N}"] = round(min(v) / N, 4)
+            for a in archs:
+                out[f"{a}_bytes_n{N}"] = len(data[a])
+                out[f"{a}_bytes_each_n{N}"] = sum(map(len, streams[a]))
+        # the mean-scale model's elementwise ops beside their scale-only counterparts, on its latents of the last x
+        m = models["MeanScaleCompressor2018"]
+        ops, sops, mops = _lib.codec_ops(), _lib.stream_ops(), _lib.mean_ops()
+        y = m.analysis_transform(x)
+        z_hat = torch.round(m.prior_analysis(y))
+        sigma, mu = m._prior(z_hat)
+        y_l, m_l = y.movedim(1, -1).contiguous(), mu.movedim(1, -1).contiguous()
+        r = mops.center_round(y_l, m_l)[0]
+        out["elementwise_ops_ms"] = {k: round(v, 4) for k, v in {
+            "symbolize_y": _events(lambda: ops.symbolize(y_l), reps),
+            "symbolize_mean_y": _events(lambda: mops.symbolize(y_l, m_l), reps),
+            "symbolize_seg_y": _events(lambda: sops.symbolize_seg(y_l, N), reps),
+            "symbolize_mean_seg_y": _events(lambda: mops.symbolize_seg(y_l, m_l, N), reps),
+            "quantize_y": _events(lambda: F.quantize(y_l, False), reps),
+            "center_round_y": _events(lambda: mops.center_round(y_l, m_l), reps),
+            "add_mean_y": _events(lambda: mops.add_mean(r, m_l), reps),
+            "h_s_sigma_only": _events(lambda: m.prior_synthesis(z_hat), reps),
+            "h_s_both_heads": _events(lambda: m._prior(z_hat), reps),
+        }.items()}
+        out["elementwise_ops_values"] = y_l.numel()
+        out["elementwise_ops_images"] = N
+    return out
 
 
 def _emit(out, path):
