@@ -207,6 +207,15 @@ SIGNATURES = {
     "ic_codec_symbolize_mean_seg": (c_int, [c_void, c_void, c_int, c_ll, c_void, c_void, P(c_int), c_void]),
     "ic_center_round": (c_int, [c_void, c_void, c_ll, c_void, c_void, c_void]),
     "ic_add_mean": (c_int, [c_void, c_void, c_ll, c_void, c_void]),
+    # checkerboard context model: anchor masks, context parameters, the halves of y (additive to ic_version 4)
+    "ic_ckbd_input_fwd": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "ic_ckbd_input_bwd": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "ic_ckbd_params_fwd": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void]),
+    "ic_ckbd_params_bwd": (c_int, [c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int, c_void, c_void, c_void,
+                                   c_void, c_void]),
+    "ic_ckbd_count": (c_ll, [c_int, c_int, c_int]),
+    "ic_ckbd_gather": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    "ic_ckbd_scatter": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
 }
 
 _lib = None
@@ -235,6 +244,12 @@ def mean_ops():
     """torch.ops.imgcomp_mean (the mean-scale hyperprior's symbolizers, quantiser and reconstruction)."""
     ops()
     return torch.ops.imgcomp_mean
+
+
+def ckbd_ops():
+    """torch.ops.imgcomp_ckbd (the checkerboard context model's masks, parameters and halves)."""
+    ops()
+    return torch.ops.imgcomp_ckbd
 
 
 def ops():

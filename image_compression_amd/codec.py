@@ -77,6 +77,22 @@ the same call (with kind 2 or 3, mu comes from the same single-image evaluation)
     tag to the chunk counts, with N = 1 and H, W the padded size,
     u32 image height h, u32 image width w   (1 <= h <= H, H - h < 64; 1 <= w <= W, W - w < 64),
     chunk lengths of z (u32 each), chunk lengths of y, payload of z, payload of y.
+
+Checkerboard container (little endian), one call = one batch = one bytes object (`CheckerboardCompressor2018`)
+--------------------------------------------------------------------------------------------------------------
+y is coded in two passes.  Position (i, j) of a latent map is an anchor when i + j is even (the parity does not
+depend on n or c).  With (sigma_h, mu_h) = h_s(z_hat): the anchors are coded as above for kind 2 or 3, symbols
+rint(y - mu_h), rows index(sigma_h).  From the decoded anchors y_hat = q + mu_h the context model gives every
+non-anchor its own (sigma, mu) (modelling/meta_arch/ckbd2021.py `_context`), and the non-anchors are coded with symbols
+rint(y - mu), rows index(sigma), reconstruction q + mu.  Each half is a bitstream of its own exactly as specified above:
+the symbols of its positions in ascending (n, i, j, c) order, chunks cut from the half's first symbol.  One K = kmax_y
+(the largest |symbol| of both halves) and so one table set serve both.
+    magic "ICRC", u16 format version (1), then the fields of the "ICRA" header from the arithmetic tag to
+    u64 symbols of y (the conditional kind is 2 or 3: 0 and 1 are rejected),
+    u32 chunks of z, u32 chunks of the anchors of y, u32 chunks of the non-anchors of y,
+    chunk lengths of z (u32 each), of the anchors, of the non-anchors, payload of z, of the anchors, of the non-anchors.
+H and W are multiples of 64, so each half holds half of y's symbols.  The three containers do not read one another:
+every parser raises ValueError on another's magic.
 """
 import math
 import struct
@@ -100,6 +116,10 @@ _HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQII")
 IMAGE_MAGIC = b"ICRP"
 IMAGE_FORMAT_VERSION = 1
 _IMAGE_HEAD = struct.Struct(_HEAD.format + "II")   # the ICRA header's fields, then image height and width
+
+CKBD_MAGIC = b"ICRC"
+CKBD_FORMAT_VERSION = 1
+_CKBD_HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQIII")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
 
 
 @dataclass
@@ -297,6 +317,112 @@ def parse_image(data, abi, compute_dtype):
         _check_image_header(h)
         return h
     return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, make)
+
+
+# ---- checkerboard container "ICRC": y in two bitstreams, the anchors and the non-anchors
+def checkerboard_count(h, w, parity):
+    """Positions (i, j) with (i + j) % 2 == parity in one h x w map (ic_ckbd_count)."""
+    if h < 1 or w < 1 or parity not in (0, 1):
+        raise ValueError(f"codec: no checkerboard half {parity} of a {h} x {w} map")
+    return (h * w + 1 - parity) // 2
+
+
+def checkerboard_order(h, w, parity):
+    """The flat positions i * w + j of one map's half `parity`, in the order the half is packed (ascending): entry
+    k by the rule of the gather / scatter kernels -- two consecutive rows hold w positions of a parity between
+    them, `first` of them in the even row."""
+    first = (w - parity + 1) // 2
+    k = np.arange(checkerboard_count(h, w, parity), dtype=np.int64)
+    pair, rem = k // w, k % w
+    odd = rem >= first
+    i = 2 * pair + odd
+    j = np.where(odd, (1 - parity) + 2 * (rem - first), parity + 2 * rem)
+    return i * w + j
+
+
+def _check_checkerboard_header(h):
+    _check_header(h)
+    if not h.kind & KIND_MEAN:
+        raise ValueError(f"codec: conditional kind {h.kind} in a checkerboard stream, which codes y about a mean (2 or 3)")
+
+
+def _half_symbols(h):
+    """(symbols of the anchor half, of the non-anchor half) of y."""
+    _, C, hh, ww = h.y_shape
+    return tuple(h.N * C * checkerboard_count(hh, ww, p) for p in (0, 1))
+
+
+def checkerboard_fixed_bytes(h):
+    """`fixed_bytes` of a checkerboard container: three streams, each half of y chunked on its own."""
+    nc = num_chunks(h.nsym_z, h.R) + sum(num_chunks(n, h.R) for n in _half_symbols(h))
+    return _CKBD_HEAD.size + 4 * nc + CHUNK_HEAD * nc
+
+
+def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn):
+    """One bytes object from the header, the three chunk-length tables and the three payloads (z, the anchors
+    of y, the non-anchors of y)."""
+    _check_checkerboard_header(h)
+    na, nn = _half_symbols(h)
+    tables, payloads = [], []
+    for name, lens, payload, nsym in (("z", lens_z, payload_z, h.nsym_z), ("y anchor", lens_ya, payload_ya, na),
+                                      ("y non-anchor", lens_yn, payload_yn, nn)):
+        lens, payload = np.ascontiguousarray(lens, dtype="<u4"), bytes(payload)
+        _check_lengths(name, lens, nsym, h.R)
+        if int(lens.sum(dtype=np.uint64)) != len(payload):
+            raise ValueError("codec: chunk lengths do not add up to the payload")
+        tables.append(lens.tobytes())
+        payloads.append(payload)
+    head = _CKBD_HEAD.pack(CKBD_MAGIC, CKBD_FORMAT_VERSION, COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H,
+                           h.W, h.latent_channels, h.hyper_channels, h.L, h.scale_min, h.scale_max, h.R, h.kmax_z,
+                           h.kmax_y, h.nsym_z, h.nsym_y, *(len(t) // 4 for t in tables))
+    return b"".join([head] + tables + payloads)
+
+
+def parse_checkerboard(data, abi, compute_dtype):
+    """(Header, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
+    `pack_checkerboard`, with the checks of `parse`.  Raises ValueError on anything inconsistent; nothing is
+    launched here."""
+    data = bytes(data)
+    if len(data) < _CKBD_HEAD.size:
+        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({_CKBD_HEAD.size})")
+    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz, nca,
+     ncn) = _CKBD_HEAD.unpack_from(data, 0)
+    if s_magic != CKBD_MAGIC:
+        raise ValueError(f"codec: bad magic {s_magic!r}")
+    if ver != CKBD_FORMAT_VERSION:
+        raise ValueError(f"codec: format version {ver}, this build reads {CKBD_FORMAT_VERSION}")
+    if dt >= len(COMPUTE_DTYPES):
+        raise ValueError(f"codec: unknown arithmetic tag {dt}")
+    if COMPUTE_DTYPES[dt] != compute_dtype:
+        raise ValueError(f"codec: stream coded with COMPUTE_DTYPE {COMPUTE_DTYPES[dt]!r}, the model runs "
+                         f"{compute_dtype!r}")
+    if s_abi != abi:
+        raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
+    h = Header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky)
+    _check_checkerboard_header(h)
+    na, nn = _half_symbols(h)
+    if nz != h.nsym_z or ny != h.nsym_y or 2 * na != ny or 2 * nn != ny:
+        raise ValueError("codec: symbol counts do not match the batch shape (y in two equal halves)")
+    counts, nsyms = (ncz, nca, ncn), (nz, na, nn)
+    if any(c != num_chunks(n, R) for c, n in zip(counts, nsyms)):
+        raise ValueError("codec: chunk counts do not match the symbol counts")
+    off = _CKBD_HEAD.size
+    if len(data) < off + 4 * sum(counts):
+        raise ValueError("codec: buffer ends inside the chunk-length tables")
+    tables = []
+    for name, c, n in zip(("z", "y anchor", "y non-anchor"), counts, nsyms):
+        lens = np.frombuffer(data, dtype="<u4", count=c, offset=off)
+        off += 4 * c
+        _check_lengths(name, lens, n, R)
+        tables.append(lens)
+    sizes = [int(t.sum(dtype=np.uint64)) for t in tables]
+    if off + sum(sizes) != len(data):
+        raise ValueError(f"codec: chunk lengths add up to {sum(sizes)} payload bytes, the buffer holds {len(data) - off}")
+    payloads = []
+    for s in sizes:
+        payloads.append(data[off:off + s])
+        off += s
+    return (h, *tables, *payloads)
 
 
 def split_packed_seg(packed, nseg, seg_len, R):

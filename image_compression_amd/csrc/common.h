@@ -17,6 +17,10 @@ typedef float floatx4v __attribute__((ext_vector_type(4)));
 #define IC_ERR_WORKSPACE 1002  // workspace too small
 #endif
 
+// checkerboard context model (ckbd.hip): the context's log-scale correction b is clamped to +-this before expf,
+// so sigma = sigma_h expf(b) stays within [1e-10 e^-4, 1e10 e^4] (functional.CKBD_LOG_SCALE_LIMIT is the same number)
+#define IC_CKBD_LOG_SCALE_LIMIT 4.0f
+
 #define IC_CHECK_LAUNCH()                                    \
   do {                                                       \
     hipError_t _e = hipGetLastError();                       \

@@ -14,6 +14,7 @@
 #include <ATen/hip/impl/HIPStreamMasqueradingAsCUDA.h>
 #include <torch/library.h>
 
+#include <climits>
 #include <tuple>
 
 #include "../../include/imgcomp.h"
@@ -1455,6 +1456,151 @@ Tensor mean_add_meta(const Tensor& r, const Tensor& mu) {
   return at::empty({r.numel()}, r.options());
 }
 
+// ---------------------------------------------------------------- checkerboard context model (imgcomp_ckbd)
+// Every full tensor is 4-D (N, H, W, C) and contiguous: the channels-last storage of a latent, position (i, j) an
+// anchor when i + j is even.  A half is flat: the elements at the positions of one parity in (n, i, j, c) order.
+void check_ckbd_shape(const Tensor& t, const char* what) {
+  TORCH_CHECK(t.dim() == 4 && t.is_contiguous() && t.numel() > 0, "imgcomp_ckbd: ", what,
+              " must be a non-empty contiguous (N, H, W, C) tensor, got ", t.sizes());
+  for (int64_t d = 0; d < 4; ++d) TORCH_CHECK(t.size(d) <= INT_MAX, "imgcomp_ckbd: ", what, " is too large: ", t.sizes());
+}
+
+void check_ckbd(const Tensor& t, const char* what) {
+  check_operand(t, what);
+  check_ckbd_shape(t, what);
+}
+
+void check_ckbd_like(const Tensor& a, const Tensor& t, const char* what) {
+  check_ckbd(t, what);
+  TORCH_CHECK(t.sizes() == a.sizes() && t.device() == a.device(), "imgcomp_ckbd: ", what, " ", t.sizes(),
+              " must have the shape ", a.sizes(), " of its partner operand, on one device");
+}
+
+void check_parity(int64_t parity) { TORCH_CHECK(parity == 0 || parity == 1, "imgcomp_ckbd: parity ", parity, " is not 0 or 1"); }
+
+int64_t ckbd_half_numel(const Tensor& full, int64_t parity) {
+  return full.size(0) * ic_ckbd_count((int)full.size(1), (int)full.size(2), (int)parity) * full.size(3);
+}
+
+#define CKBD_DIMS(t) (int)(t).size(0), (int)(t).size(1), (int)(t).size(2), (int)(t).size(3)
+
+std::tuple<Tensor, Tensor> ckbd_input_fwd(const Tensor& y, const Tensor& mu) {
+  check_ckbd(y, "y");
+  check_ckbd_like(y, mu, "mu");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor u = at::empty_like(y), v = at::empty_like(y);
+  check_rc(ic_ckbd_input_fwd(y.data_ptr<float>(), mu.data_ptr<float>(), CKBD_DIMS(y), u.data_ptr<float>(),
+                             v.data_ptr<float>(), stream_of(y)),
+           "ckbd_input_fwd");
+  return {u, v};
+}
+
+std::tuple<Tensor, Tensor> ckbd_input_bwd(const Tensor& y, const Tensor& mu, const Tensor& du, const Tensor& dv) {
+  check_ckbd(y, "y");
+  check_ckbd_like(y, mu, "mu");
+  check_ckbd_like(y, du, "du");
+  check_ckbd_like(y, dv, "dv");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor dy = at::empty_like(y), dmu = at::empty_like(y);
+  check_rc(ic_ckbd_input_bwd(y.data_ptr<float>(), mu.data_ptr<float>(), du.data_ptr<float>(), dv.data_ptr<float>(),
+                             CKBD_DIMS(y), dy.data_ptr<float>(), dmu.data_ptr<float>(), stream_of(y)),
+           "ckbd_input_bwd");
+  return {dy, dmu};
+}
+
+std::tuple<Tensor, Tensor> ckbd_params_fwd(const Tensor& mu_h, const Tensor& sigma_h, const Tensor& a, const Tensor& b) {
+  check_ckbd(mu_h, "mu_h");
+  check_ckbd_like(mu_h, sigma_h, "sigma_h");
+  check_ckbd_like(mu_h, a, "a");
+  check_ckbd_like(mu_h, b, "b");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(mu_h.device());
+  Tensor mu = at::empty_like(mu_h), sigma = at::empty_like(mu_h);
+  check_rc(ic_ckbd_params_fwd(mu_h.data_ptr<float>(), sigma_h.data_ptr<float>(), a.data_ptr<float>(), b.data_ptr<float>(),
+                              CKBD_DIMS(mu_h), mu.data_ptr<float>(), sigma.data_ptr<float>(), stream_of(mu_h)),
+           "ckbd_params_fwd");
+  return {mu, sigma};
+}
+
+std::tuple<Tensor, Tensor, Tensor, Tensor> ckbd_params_bwd(const Tensor& sigma_h, const Tensor& b, const Tensor& dmu,
+                                                           const Tensor& dsigma) {
+  check_ckbd(sigma_h, "sigma_h");
+  check_ckbd_like(sigma_h, b, "b");
+  check_ckbd_like(sigma_h, dmu, "dmu");
+  check_ckbd_like(sigma_h, dsigma, "dsigma");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sigma_h.device());
+  Tensor dmu_h = at::empty_like(b), dsigma_h = at::empty_like(b), da = at::empty_like(b), db = at::empty_like(b);
+  check_rc(ic_ckbd_params_bwd(sigma_h.data_ptr<float>(), b.data_ptr<float>(), dmu.data_ptr<float>(),
+                              dsigma.data_ptr<float>(), CKBD_DIMS(b), dmu_h.data_ptr<float>(), dsigma_h.data_ptr<float>(),
+                              da.data_ptr<float>(), db.data_ptr<float>(), stream_of(b)),
+           "ckbd_params_bwd");
+  return {dmu_h, dsigma_h, da, db};
+}
+
+// src uint8 (table rows), int32 (symbols) or float32
+Tensor ckbd_gather(const Tensor& src, int64_t parity) {
+  TORCH_CHECK(src.is_cuda(), "imgcomp_ckbd: src must be on a ROCm device, got ", src.device());
+  const auto ty = src.scalar_type();
+  TORCH_CHECK(ty == at::kByte || ty == at::kInt || ty == at::kFloat, "imgcomp_ckbd: src must be uint8, int32 or float32, got ",
+              ty);
+  check_ckbd_shape(src, "src");
+  check_parity(parity);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+  Tensor half = at::empty({ckbd_half_numel(src, parity)}, src.options());
+  if (half.numel() == 0) return half;   // a 1 x 1 map has no non-anchor
+  check_rc(ic_ckbd_gather(src.data_ptr(), (int)src.element_size(), CKBD_DIMS(src), (int)parity, half.data_ptr(),
+                          stream_of(src)),
+           "ckbd_gather");
+  return half;
+}
+
+void ckbd_scatter(const Tensor& half, Tensor& full, int64_t parity) {
+  check_ckbd(full, "full");
+  check_operand(half, "half");
+  check_parity(parity);
+  TORCH_CHECK(half.is_contiguous() && half.device() == full.device() && half.numel() == ckbd_half_numel(full, parity),
+              "imgcomp_ckbd: the half (", half.numel(), " values) must be contiguous, on full's device and hold its ",
+              ckbd_half_numel(full, parity), " values of parity ", parity);
+  if (half.numel() == 0) return;
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(full.device());
+  check_rc(ic_ckbd_scatter(half.data_ptr<float>(), CKBD_DIMS(full), (int)parity, full.data_ptr<float>(), stream_of(full)),
+           "ckbd_scatter");
+}
+
+void check_ckbd_meta(const Tensor& a, std::initializer_list<const Tensor*> rest) {
+  check_ckbd_shape(a, "the first operand");
+  for (const Tensor* t : rest)
+    TORCH_CHECK(t->sizes() == a.sizes(), "imgcomp_ckbd: operands must have the same shape, got ", a.sizes(), " and ",
+                t->sizes());
+}
+std::tuple<Tensor, Tensor> ckbd_input_fwd_meta(const Tensor& y, const Tensor& mu) {
+  check_ckbd_meta(y, {&mu});
+  return {at::empty_like(y), at::empty_like(y)};
+}
+std::tuple<Tensor, Tensor> ckbd_input_bwd_meta(const Tensor& y, const Tensor& mu, const Tensor& du, const Tensor& dv) {
+  check_ckbd_meta(y, {&mu, &du, &dv});
+  return {at::empty_like(y), at::empty_like(y)};
+}
+std::tuple<Tensor, Tensor> ckbd_params_fwd_meta(const Tensor& mu_h, const Tensor& sigma_h, const Tensor& a, const Tensor& b) {
+  check_ckbd_meta(mu_h, {&sigma_h, &a, &b});
+  return {at::empty_like(mu_h), at::empty_like(mu_h)};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> ckbd_params_bwd_meta(const Tensor& sigma_h, const Tensor& b, const Tensor& dmu,
+                                                                const Tensor& dsigma) {
+  check_ckbd_meta(sigma_h, {&b, &dmu, &dsigma});
+  return {at::empty_like(b), at::empty_like(b), at::empty_like(b), at::empty_like(b)};
+}
+Tensor ckbd_gather_meta(const Tensor& src, int64_t parity) {
+  check_ckbd_shape(src, "src");
+  check_parity(parity);
+  return at::empty({ckbd_half_numel(src, parity)}, src.options());
+}
+void ckbd_scatter_meta(const Tensor& half, Tensor& full, int64_t parity) {
+  check_ckbd_shape(full, "full");
+  check_parity(parity);
+  TORCH_CHECK(half.numel() == ckbd_half_numel(full, parity), "imgcomp_ckbd: the half (", half.numel(),
+              " values) must hold full's ", ckbd_half_numel(full, parity), " values of parity ", parity);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1706,4 +1852,32 @@ TORCH_LIBRARY_IMPL(imgcomp_mean, Meta, m) {
   m.impl("symbolize_seg", mean_symbolize_seg_meta);
   m.impl("center_round", mean_center_round_meta);
   m.impl("add_mean", mean_add_meta);
+}
+
+// The checkerboard context model's ops (CheckerboardCompressor2018): additive, in a namespace of their own.
+TORCH_LIBRARY(imgcomp_ckbd, m) {
+  m.def("input_fwd(Tensor y, Tensor mu) -> (Tensor, Tensor)");
+  m.def("input_bwd(Tensor y, Tensor mu, Tensor du, Tensor dv) -> (Tensor, Tensor)");
+  m.def("params_fwd(Tensor mu_h, Tensor sigma_h, Tensor a, Tensor b) -> (Tensor, Tensor)");
+  m.def("params_bwd(Tensor sigma_h, Tensor b, Tensor dmu, Tensor dsigma) -> (Tensor, Tensor, Tensor, Tensor)");
+  m.def("gather(Tensor src, int parity) -> Tensor");
+  m.def("scatter(Tensor half, Tensor(a!) full, int parity) -> ()");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_ckbd, CUDA, m) {
+  m.impl("input_fwd", ckbd_input_fwd);
+  m.impl("input_bwd", ckbd_input_bwd);
+  m.impl("params_fwd", ckbd_params_fwd);
+  m.impl("params_bwd", ckbd_params_bwd);
+  m.impl("gather", ckbd_gather);
+  m.impl("scatter", ckbd_scatter);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_ckbd, Meta, m) {
+  m.impl("input_fwd", ckbd_input_fwd_meta);
+  m.impl("input_bwd", ckbd_input_bwd_meta);
+  m.impl("params_fwd", ckbd_params_fwd_meta);
+  m.impl("params_bwd", ckbd_params_bwd_meta);
+  m.impl("gather", ckbd_gather_meta);
+  m.impl("scatter", ckbd_scatter_meta);
 }

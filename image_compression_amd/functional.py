@@ -867,6 +867,75 @@ def conditional(y, scale, mean, kind, train, u=None, bin_=1.0):
     return ConditionalFn.apply(y, scale, mean, kind, mode, u, seed, off, float(bin_))
 
 
+# ============================================================== checkerboard context model
+CKBD_LOG_SCALE_LIMIT = 4.0   # IC_CKBD_LOG_SCALE_LIMIT (csrc/common.h): the clamp of the context's log-scale correction
+
+
+def _ckbd_last(t):
+    """(N, C, H, W) -> the contiguous (N, H, W, C) tensor the checkerboard ops index (no copy when channels-last)."""
+    if t.dim() != 4:
+        raise ValueError(f"the checkerboard ops take (N, C, H, W) tensors, got {tuple(t.shape)}")
+    return _to_last(t)
+
+
+def _ckbd_pair(ref, *ts):
+    _lib.require_device(ref, *ts)
+    for t in ts:
+        if tuple(t.shape) != tuple(ref.shape):
+            raise ValueError(f"checkerboard operands must share one shape, got {tuple(ref.shape)} and {tuple(t.shape)}")
+    return [_ckbd_last(t) for t in (ref, *ts)]
+
+
+class CkbdInputFn(Function):
+    """(u, v) = (y, |y - mu|) at the anchors (positions with i + j even), +0.0 elsewhere: the inputs of the
+    context convs (torch.ops.imgcomp_ckbd.input_fwd / input_bwd)."""
+
+    @staticmethod
+    def forward(ctx, y, mu):
+        yl, ml = _ckbd_pair(y, mu)
+        ctx.save_for_backward(yl, ml)
+        u, v = _lib.ckbd_ops().input_fwd(yl, ml)
+        return _from_last(u), _from_last(v)
+
+    @staticmethod
+    def backward(ctx, gu, gv):
+        yl, ml = ctx.saved_tensors
+        gu = torch.zeros_like(yl) if gu is None else _ckbd_last(gu)
+        gv = torch.zeros_like(yl) if gv is None else _ckbd_last(gv)
+        dy, dmu = _lib.ckbd_ops().input_bwd(yl, ml, gu, gv)
+        return _from_last(dy), _from_last(dmu)
+
+
+class CkbdParamsFn(Function):
+    """(mu, sigma) = (mu_h + a, sigma_h * exp(clamp(b, -L, L))) at the non-anchors, (mu_h, sigma_h) bit for bit
+    at the anchors, L = CKBD_LOG_SCALE_LIMIT (torch.ops.imgcomp_ckbd.params_fwd / params_bwd)."""
+
+    @staticmethod
+    def forward(ctx, mu_h, sigma_h, a, b):
+        ml, sl, al, bl = _ckbd_pair(mu_h, sigma_h, a, b)
+        ctx.save_for_backward(sl, bl)
+        mu, sigma = _lib.ckbd_ops().params_fwd(ml, sl, al, bl)
+        return _from_last(mu), _from_last(sigma)
+
+    @staticmethod
+    def backward(ctx, gmu, gsigma):
+        sl, bl = ctx.saved_tensors
+        gmu = torch.zeros_like(sl) if gmu is None else _ckbd_last(gmu)
+        gsigma = torch.zeros_like(sl) if gsigma is None else _ckbd_last(gsigma)
+        dmu_h, dsigma_h, da, db = _lib.ckbd_ops().params_bwd(sl, bl, gmu, gsigma)
+        return _from_last(dmu_h), _from_last(dsigma_h), _from_last(da), _from_last(db)
+
+
+def ckbd_input(y, mu):
+    """The context convs' inputs (u, v) from the quantised latent and the hyperprior's mean (CkbdInputFn)."""
+    return CkbdInputFn.apply(y, mu)
+
+
+def ckbd_params(mu_h, sigma_h, a, b):
+    """(mu, sigma): the hyperprior's parameters with the context's corrections at the non-anchors (CkbdParamsFn)."""
+    return CkbdParamsFn.apply(mu_h, sigma_h, a, b)
+
+
 class SqDiffFn(Function):
     """(a - b)^2 elementwise: nn.MSELoss(reduction='none')."""
 

@@ -20,6 +20,7 @@ from ... import _lib
 from ... import codec as _codec
 from ... import noise as _noise
 from ...functional import CELossFn, _to_last, conditional, conditional_likelihood, factorized, quantize
+from ...functional import ckbd_input as _ckbd_input, ckbd_params as _ckbd_params
 from .build import ENTROPY_MODEL_REGISTRY
 
 LOG2 = math.log(2.0)
@@ -144,6 +145,44 @@ def add_mean(flat, mean):
     integers r in (n, *, c) order, as the (N, C, *) tensor over that storage."""
     _lib.require_device(flat, mean)
     return symbols_as_tensor(_lib.mean_ops().add_mean(flat, _to_last(mean)), tuple(mean.shape))
+
+
+# ---- checkerboard context model: position (i, j) of a latent map is an anchor when i + j is even (parity 0)
+def ckbd_input(y, mean):
+    """(u, v): y and |y - mean| (one fp32 subtraction) at the anchors, +0.0 elsewhere -- what the context convs
+    read.  Differentiable in y and mean."""
+    return _ckbd_input(y, mean.expand_as(y))
+
+
+def ckbd_params(mean_h, sigma_h, a, b):
+    """(mean, sigma): (mean_h + a, sigma_h * exp(clamp(b, -4, 4))) at the non-anchors, the hyperprior's own
+    (mean_h, sigma_h) bit for bit at the anchors.  Differentiable in all four."""
+    return _ckbd_params(mean_h, sigma_h.expand_as(mean_h), a, b)
+
+
+def _ckbd_view(flat, shape):
+    N, C, H, W = shape
+    if flat.numel() != N * C * H * W:
+        raise ValueError(f"{flat.numel()} values are not a latent of shape {tuple(shape)}")
+    return flat.contiguous().view(N, H, W, C)
+
+
+def ckbd_gather(flat, shape, parity):
+    """The values of `flat` (a latent of logical `shape` (N, C, H, W) flattened in (n, i, j, c) order: float
+    values, int32 symbols or uint8 table rows) at the positions of `parity`, packed in that same order."""
+    if not flat.is_cuda:
+        raise RuntimeError(f"imgcomp: HIP kernels need tensors on a ROCm (cuda) device; got a tensor on {flat.device}")
+    return _lib.ckbd_ops().gather(_ckbd_view(flat, shape), int(parity))
+
+
+def ckbd_scatter(half, flat, shape, parity):
+    """Writes the packed float values `half` of `parity` to their positions of `flat` (in place; the other parity
+    keeps its values) and returns `flat`."""
+    _lib.require_device(half, flat)
+    if not flat.is_contiguous():
+        raise ValueError("ckbd_scatter writes in place: the full tensor must be contiguous")
+    _lib.ckbd_ops().scatter(half.contiguous(), _ckbd_view(flat, shape), int(parity))
+    return flat
 
 
 def symbols_as_tensor(flat, shape):

@@ -41,7 +41,8 @@ def set_compute_dtype(model, dtype):
     if dtype not in MATH:
         raise ValueError(f"compute dtype {dtype!r}: expected one of {sorted(MATH)}")
     main = ("analysis_transform", "synthesis_transform")
-    hyper = ("prior_analysis", "prior_synthesis", "prior_mean")   # prior_mean: MeanScaleCompressor2018's second h_s head
+    # prior_mean: MeanScaleCompressor2018's second h_s head; context_*: CheckerboardCompressor2018's two context convs
+    hyper = ("prior_analysis", "prior_synthesis", "prior_mean", "context_mean", "context_scale")
     # IC_MATH_* per transform: bf16 (C3) falls back to split arithmetic (fp32-accurate,
     # faster than the fp32 MFMA) where no bf16 kernel applies, and runs the hyperprior split
     split = MATH["fp32_split"]

@@ -1,0 +1,165 @@
+"""CheckerboardCompressor2018 -- MeanScaleCompressor2018 with the checkerboard context model of He et al. 2021
+("Checkerboard Context Model for Efficient Learned Image Compression"): the context model of Minnen et al. 2018 in
+a form that decodes in two parallel passes instead of one serial scan.
+
+Position (i, j) of the latent map is an anchor when i + j is even.  The anchors are coded from the hyperprior
+alone, (sigma_h, mu_h) = h_s(z_hat); every non-anchor is coded with parameters that also depend on the decoded
+anchors in the 5 x 5 window around it (`_context`):
+    u, v = anchors of y_hat, anchors of |y_hat - mu_h|          (+0.0 at the non-anchors)
+    mu    = mu_h + context_mean(u)                              at the non-anchors, mu_h at the anchors
+    sigma = sigma_h * exp(clamp(context_scale(v), -4, 4))       at the non-anchors, sigma_h at the anchors
+Both heads are single linear 5 x 5 convs: the mean is predicted from the neighbours' values, the log-scale from
+the magnitudes of their residuals.  Their weights and biases start at zero, so a freshly built model is exactly the
+mean-scale model (and a mean-scale checkpoint, loaded with strict=False, is a converted model: the four missing
+tensors are the zero context, which changes nothing) and the context is learnt from there.
+
+No weight mask.  The usual checkerboard convolution masks the 13 of 25 taps (di, dj) with di + dj even, which read
+a non-anchor from a non-anchor.  Here those taps contribute exactly 0 to every value that is used, because u and v
+are zero at the non-anchors and the convs' outputs at the anchors are discarded; and they receive a gradient of
+exactly 0, because in every product of their weight gradient either the output gradient (an anchor output) or the
+input (a non-anchor input) is zero.  So they stay at their initial zero without being masked.  (They still cost
+their multiply-adds)
+
+Decodability: the contract of Compressor2018.decompress (same weights, build, COMPUTE_DTYPE, device type and batch
+shape) and nothing more.  The two sides agree bit for bit on the non-anchors' (sigma, mu) because the decoder's
+`add_mean` is `center_round`'s addition, so u and v are identical at the anchors and +0.0 elsewhere on both sides,
+and the convs are deterministic for a given shape, arithmetic and build."""
+import torch
+import torch.nn as nn
+
+from ... import _lib
+from ... import codec as _codec
+from ... import noise as _noise
+from ...functional import conditional_likelihood
+from ..blocks.entropy_model import (_decode, _encode, add_mean, center_round, ckbd_gather, ckbd_input, ckbd_params,
+                                    ckbd_scatter, symbolize, symbolize_mean, symbols_as_tensor)
+from ..layers import Conv2d, LowerBound, UpperBound
+from .build import META_ARCH_REGISTRY
+from .mshp2018 import MeanScaleCompressor2018
+
+
+@META_ARCH_REGISTRY.register()
+class CheckerboardCompressor2018(MeanScaleCompressor2018):
+    """The mean-scale hyperprior plus two 5 x 5 context convs over the anchors (see the module docstring).  The
+    convs carry no weight mask and need none: their inputs are zero at the non-anchors and their outputs at the
+    anchors are discarded, so the 13 taps (di, dj) with di + dj even contribute exactly 0 to every value that is
+    used and receive a gradient of exactly 0.  State dict: MeanScaleCompressor2018's plus
+    context_mean.{weight,bias} and context_scale.{weight,bias}, all zero in a fresh model."""
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        # after every inherited module: their initial values are MeanScaleCompressor2018's from the same seed
+        M = cfg.MODEL.LATENT_CHANNELS
+        self.context_mean = Conv2d(M, M, 5, stride=1, padding=2)
+        self.context_scale = Conv2d(M, M, 5, stride=1, padding=2)
+        for conv in (self.context_mean, self.context_scale):
+            nn.init.zeros_(conv.weight.data)
+            nn.init.zeros_(conv.bias.data)
+
+    def _context(self, y_in, sigma_h, mu_h):
+        """(sigma, mu) of every position from the hyperprior's (sigma_h, mu_h) and the anchors of y_in; the whole
+        dependence on neighbours is here.  y_in's non-anchors are not read."""
+        u, v = ckbd_input(y_in, mu_h)
+        mu, sigma = ckbd_params(mu_h, sigma_h, self.context_mean(u), self.context_scale(v))
+        return sigma, mu
+
+    def _eval_params(self, y, sigma_h, mu_h):
+        """(sigma, mu) as the decoder will hold them: the context of the anchors as decoded, rint(y - mu_h) + mu_h."""
+        _, y_anchor = center_round(y, mu_h.expand_as(y))
+        return self._context(y_anchor, sigma_h.expand_as(y), mu_h.expand_as(y))
+
+    def _forward(self, x):
+        cm = self.conditional_model
+        if self.training:
+            _noise.begin_step(x.device)  # fresh Philox counters for this step
+        elif float(cm.bin) != 1.0:
+            raise NotImplementedError(f"the eval forward rounds the residual to integers: BIN must be 1, got {cm.bin}")
+        self._reparameterise_gdn(x)
+        N, _, H, W = x.shape
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(y)
+        z_tilde, _z_probs, z_ce = self.entropy_model(z)
+        sigma_h, mu_h = self._prior(z_tilde)
+        if self.training:
+            y_tilde = cm.quantize(y)
+            sigma, mu = self._context(y_tilde, sigma_h.expand_as(y), mu_h.expand_as(y))
+            y_probs = conditional_likelihood(y_tilde, sigma, mu, cm.KIND, cm.bin)
+        else:
+            sigma, mu = self._eval_params(y, sigma_h, mu_h)
+            r, y_tilde = center_round(y, mu)   # at the anchors mu is mu_h bit for bit: one call serves both halves
+            y_probs = cm.likelihood(r, sigma)
+        y_ce = cm._ce_loss(y_probs)
+        x_tilde = self.synthesis_transform(y_tilde)
+        x_tilde = LowerBound.apply(UpperBound.apply(x_tilde, 1.), 0.)
+        dist = self.distortion_loss(x, x_tilde)
+        return x_tilde.detach(), self._losses(z_ce, y_ce, dist, N * H * W)
+
+    # ---- bitstreams: container "ICRC" (codec.py), y as two streams -- the anchors, then the non-anchors
+    @torch.no_grad()
+    def compress(self, x, steps_per_chunk=1024):
+        """x (N, 3, H, W) in [0, 1], H and W multiples of 64 -> one bytes object for the batch."""
+        self._codable_each()
+        if x.dim() != 4 or x.shape[2] % _codec.Z_DOWN or x.shape[3] % _codec.Z_DOWN:
+            raise ValueError(f"compress: image size {tuple(x.shape)} must be (N, C, H, W) with H and W "
+                             f"multiples of {_codec.Z_DOWN}")
+        em, cm = self.entropy_model, self.conditional_model
+        N, _, H, W = x.shape
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(self._hyper_input(y))
+        z_sym, kz = symbolize(z)
+        # (sigma_h, mu_h) from the integers the decoder will hold, then the context of the anchors as it decodes them
+        sigma_h, mu_h = self._prior(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
+        pz, lz = em.encode_symbols(z_sym, kz, steps_per_chunk)
+        sigma, mu = self._eval_params(y, sigma_h, mu_h)
+        y_sym, ky = symbolize_mean(y, mu)       # one K and one table set for both halves
+        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], self._stream_kind(), getattr(self, "compute_dtype", "fp32"),
+                          int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max, int(steps_per_chunk),
+                          kz, ky)
+        if tuple(z.shape) != h.z_shape or tuple(y.shape) != h.y_shape:
+            raise ValueError(f"compress: latents {tuple(y.shape)} / {tuple(z.shape)} are not the image size over "
+                             f"{_codec.Y_DOWN} / {_codec.Z_DOWN}")
+        rows, tables = cm.scale_rows(sigma), cm.tables(ky, y.device)
+        halves = [_encode(ckbd_gather(y_sym, h.y_shape, p), ckbd_gather(rows, h.y_shape, p), 0, tables, steps_per_chunk)
+                  for p in (0, 1)]
+        (pa, la), (pn, ln) = halves
+        return _codec.pack_checkerboard(h, lz, la, ln, pz, pa, pn)
+
+    @torch.no_grad()
+    def decompress(self, data):
+        """bytes from `compress` (same weights, build, COMPUTE_DTYPE, device type and batch shape) ->
+        x_hat (N, 3, H, W), the eval forward's reconstruction.  Two passes: the anchors from the hyperprior, then the
+        non-anchors from the hyperprior and the decoded anchors."""
+        self._codable_each()
+        em, cm = self.entropy_model, self.conditional_model
+        h, lz, la, ln, pz, pa, pn = _codec.parse_checkerboard(data, int(_lib.load().ic_version()),
+                                                              getattr(self, "compute_dtype", "fp32"))
+        if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
+            raise ValueError("decompress: the stream was coded by a different model (conditional kind / channels)")
+        if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
+            raise ValueError("decompress: the stream was coded with a different scale table")
+        z_hat = em.decompress(pz, h.z_shape, lz, h.kmax_z, h.R)
+        sigma_h, mu_h = self._prior(z_hat)
+        if tuple(sigma_h.shape) != h.y_shape or tuple(mu_h.shape) != h.y_shape:
+            raise ValueError(f"decompress: the model's sigma {tuple(sigma_h.shape)} is not the stream's latent shape "
+                             f"{h.y_shape}")
+        dev, half = sigma_h.device, h.nsym_y // 2
+        tables = cm.tables(h.kmax_y, dev)
+        flat = torch.zeros(h.nsym_y, dtype=torch.float32, device=dev)
+        # pass one: the anchors, coded under the hyperprior's own parameters
+        rows = ckbd_gather(cm.scale_rows(sigma_h), h.y_shape, 0)
+        ckbd_scatter(_decode(pa, la, half, rows, 0, tables, h.R, dev), flat, h.y_shape, 0)
+        sigma, mu = self._context(add_mean(flat, mu_h), sigma_h, mu_h)
+        # pass two: the non-anchors, under the parameters the decoded anchors give them
+        rows = ckbd_gather(cm.scale_rows(sigma), h.y_shape, 1)
+        ckbd_scatter(_decode(pn, ln, half, rows, 0, tables, h.R, dev), flat, h.y_shape, 1)
+        x_hat = self.synthesis_transform(add_mean(flat, mu))
+        return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)
+
+    # Per-image streams need the context convs run one image at a time on both sides, as h_s is (`_prior_each`): not built.
+    def compress_each(self, x, steps_per_chunk=1024):
+        self._codable()
+        raise NotImplementedError("CheckerboardCompressor2018 has no per-image streams (compress_each): use compress")
+
+    def decompress_each(self, streams):
+        self._codable()
+        raise NotImplementedError("CheckerboardCompressor2018 has no per-image streams (decompress_each): use decompress")

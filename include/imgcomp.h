@@ -560,6 +560,32 @@ int ic_center_round(const float* y, const float* mu, long long n, float* r, floa
 /* y_hat[i] = r[i] + mu[i]: the decoder's reconstruction from the float integers r it decoded */
 int ic_add_mean(const float* r, const float* mu, long long n, float* y_hat, void* stream);
 
+/* ---- checkerboard context model (additive to version 4).  Every tensor is dense channels-last storage
+ *      (n, i, j, c) of N x H x W x C elements (H, W: the latent map's), indexed in 64 bits; position (i, j) is an
+ *      anchor when i + j is even, whatever n and c.  `parity` 0 names the anchors, 1 the non-anchors.  IC_ERR_ARG
+ *      before any launch for a null pointer, a size below 1, N H W C past 2^63 - 1, a parity outside {0, 1} or
+ *      outputs that share a buffer.  None of them allocates or waits for its stream. ---- */
+/* the context convs' inputs: u = y and v = |y - mu| (one fp32 subtraction) at the anchors, +0.0 elsewhere */
+int ic_ckbd_input_fwd(const float* y, const float* mu, int N, int H, int W, int C, float* u, float* v, void* stream);
+/* with s = sign(y - mu) (0 at 0) at the anchors: dy = du + s dv, dmu = -s dv; +0.0 elsewhere */
+int ic_ckbd_input_bwd(const float* y, const float* mu, const float* du, const float* dv, int N, int H, int W, int C,
+                      float* dy, float* dmu, void* stream);
+/* mu = mu_h + a and sigma = sigma_h expf(clamp(b, -4, 4)) at the non-anchors; mu_h and sigma_h, bit for bit, at the
+ * anchors */
+int ic_ckbd_params_fwd(const float* mu_h, const float* sigma_h, const float* a, const float* b, int N, int H, int W, int C,
+                       float* mu, float* sigma, void* stream);
+/* dmu_h = dmu; with e = expf(clamp(b)) at the non-anchors da = dmu, dsigma_h = dsigma e, db = dsigma sigma_h e where
+ * -4 <= b <= 4 and 0 beyond; at the anchors da = db = 0, dsigma_h = dsigma */
+int ic_ckbd_params_bwd(const float* sigma_h, const float* b, const float* dmu, const float* dsigma, int N, int H, int W,
+                       int C, float* dmu_h, float* dsigma_h, float* da, float* db, void* stream);
+/* positions of that parity in one H x W map (any H, W >= 1); -1: bad arguments */
+long long ic_ckbd_count(int H, int W, int parity);
+/* dst = the elements (elem_bytes 1 or 4 wide) of src at the positions of that parity, packed in ascending
+ * (n, i, j, c) order: N * ic_ckbd_count(H, W, parity) * C elements */
+int ic_ckbd_gather(const void* src, int elem_bytes, int N, int H, int W, int C, int parity, void* dst, void* stream);
+/* the inverse for floats: writes the packed half to its positions of `full`, the other parity untouched */
+int ic_ckbd_scatter(const float* half, int N, int H, int W, int C, int parity, float* full, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

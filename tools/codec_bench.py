@@ -10,7 +10,8 @@ symbols of the same image.  One JSON line; --out also writes it to a file.
     python tools/codec_bench.py --compare 8 [--reps 10] [--scale 32] [--out FILE]
 
 --arch NAME (default Compressor2018) runs the two modes above on another registered model, e.g.
-MeanScaleCompressor2018; the output then carries an "arch" key.
+MeanScaleCompressor2018; the output then carries an "arch" key.  For CheckerboardCompressor2018 (another container,
+no per-image streams) the first mode reports the forward, compress and decompress times and the bytes only.
 
 --compare N times Compressor2018 and MeanScaleCompressor2018 alternately in one process: compress / decompress
 and compress_each / decompress_each at 1 and N images of --height x --width (ms per image, best of --reps), the
@@ -202,6 +203,15 @@ def main():
         t_fwd = wall(lambda: model(x))
         t_c = wall(lambda: model.compress(x))
         t_d = wall(lambda: model.decompress(data))
+        if data[:4] != codec.MAGIC:
+            # another container (CheckerboardCompressor2018's "ICRC", y in two streams): the three calls only
+            _emit(tag({"metric": f"compress / decompress ms per image ({args.height}x{args.width}, batch 1, weight cache)",
+                       "unit": "ms", "forward_ms": round(t_fwd, 3), "compress_ms": round(t_c, 3),
+                       "decompress_ms": round(t_d, 3), "bytes": len(data),
+                       "coded_bpp": round(8 * len(data) / (args.height * args.width), 5),
+                       "container": data[:4].decode(), "decompress_equals_forward": same, "weight_scale": args.scale,
+                       "reps": args.reps, "compute_dtype": cfg.MODEL.COMPUTE_DTYPE}), args.out)
+            return
         # the coder's ops alone, on this image's latents
         h = codec.parse(data, int(_lib.load().ic_version()), cfg.MODEL.COMPUTE_DTYPE)[0]
         y = model.analysis_transform(x)
