@@ -111,15 +111,16 @@ CHUNK_HEAD = 256           # 64 lanes x 4 bytes of state
 COMPUTE_DTYPES = ("fp32_split", "fp32", "bf16")
 Y_DOWN, Z_DOWN = 16, 64    # image pixels per latent / hyper-latent sample, each way
 
-_HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQII")
+_FIELDS = "<4sHBBIIIIIIIddIIIQQ"   # what every container's header starts with: magic .. symbols of y; chunk counts follow
+_HEAD = struct.Struct(_FIELDS + "II")
 
 IMAGE_MAGIC = b"ICRP"
 IMAGE_FORMAT_VERSION = 1
-_IMAGE_HEAD = struct.Struct(_HEAD.format + "II")   # the ICRA header's fields, then image height and width
+_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II")   # the ICRA header's fields, then image height and width
 
 CKBD_MAGIC = b"ICRC"
 CKBD_FORMAT_VERSION = 1
-_CKBD_HEAD = struct.Struct("<4sHBBIIIIIIIddIIIQQIII")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
+_CKBD_HEAD = struct.Struct(_FIELDS + "III")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
 
 
 @dataclass
@@ -180,13 +181,6 @@ def scale_table(L, scale_min, scale_max):
     return np.asarray(s, dtype=np.float32), np.asarray(mids, dtype=np.float32)
 
 
-def fixed_bytes(h):
-    """The bytes of a container that do not depend on the symbols: header, length tables and the
-    256 bytes of lane states per chunk."""
-    nc = num_chunks(h.nsym_z, h.R) + num_chunks(h.nsym_y, h.R)
-    return _HEAD.size + 4 * nc + CHUNK_HEAD * nc
-
-
 def _check_header(h):
     if h.compute_dtype not in COMPUTE_DTYPES:
         raise ValueError(f"codec: unknown COMPUTE_DTYPE {h.compute_dtype!r}")
@@ -218,35 +212,43 @@ def _check_lengths(name, lens, nsym, R):
             raise ValueError(f"codec: {name} chunk {c} of {words} symbols cannot be {n} bytes long")
 
 
-def _pack_body(h, lens_z, lens_y, payload_z, payload_y):
-    """The checked length tables and payloads of a container, and the header fields both containers share."""
-    lens_z = np.ascontiguousarray(lens_z, dtype="<u4")
-    lens_y = np.ascontiguousarray(lens_y, dtype="<u4")
-    payload_z, payload_y = bytes(payload_z), bytes(payload_y)
-    _check_lengths("z", lens_z, h.nsym_z, h.R)
-    _check_lengths("y", lens_y, h.nsym_y, h.R)
-    if int(lens_z.sum(dtype=np.uint64)) != len(payload_z) or int(lens_y.sum(dtype=np.uint64)) != len(payload_y):
+# ---- the framing all three containers share: header, one chunk-length table per stream, one payload per stream.
+# The first stream is z; the streams of y are named by `y_names` and hold `y_symbols(h)` symbols.
+def _whole_y(h):
+    return (h.nsym_y,)
+
+
+def _fixed_bytes(head, h, y_symbols=_whole_y):
+    nc = sum(num_chunks(n, h.R) for n in (h.nsym_z, *y_symbols(h)))
+    return head.size + 4 * nc + CHUNK_HEAD * nc
+
+
+def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y",), y_symbols=_whole_y):
+    """One bytes object from the header `h`, which `check` passes, the streams' chunk-length tables and their
+    payloads; `extra`: the header fields after the chunk counts."""
+    check(h)
+    lens = [np.ascontiguousarray(l, dtype="<u4") for l in lens]
+    payloads = [bytes(p) for p in payloads]
+    for name, l, nsym in zip(("z", *y_names), lens, (h.nsym_z, *y_symbols(h))):
+        _check_lengths(name, l, nsym, h.R)
+    if any(int(l.sum(dtype=np.uint64)) != len(p) for l, p in zip(lens, payloads)):
         raise ValueError("codec: chunk lengths do not add up to the payload")
     fields = (COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W, h.latent_channels, h.hyper_channels,
-              h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y, h.nsym_z, h.nsym_y, len(lens_z), len(lens_y))
-    return fields, (lens_z.tobytes(), lens_y.tobytes(), payload_z, payload_y)
+              h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y, h.nsym_z, h.nsym_y, *map(len, lens), *extra)
+    return b"".join([head.pack(magic, version, *fields)] + [l.tobytes() for l in lens] + payloads)
 
 
-def pack(h, lens_z, lens_y, payload_z, payload_y):
-    """One bytes object from the header, the two chunk-length tables and the two payloads."""
-    _check_header(h)
-    fields, body = _pack_body(h, lens_z, lens_y, payload_z, payload_y)
-    return b"".join((_HEAD.pack(MAGIC, FORMAT_VERSION, *fields),) + body)
-
-
-def _parse(data, abi, compute_dtype, head, magic, version, make_header):
-    """What `parse` and `parse_image` share: the header `head` with its magic and version, the checks of the
-    header `make_header(common fields, extra fields)` returns, the length tables and the payloads."""
+def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_names=("y",), y_symbols=_whole_y, note=""):
+    """(header, the streams' chunk-length tables, their payloads) of a container: the header `head` with its magic
+    and version, the header object `header(common fields, fields after the chunk counts)` passed through `check`,
+    and every check of the counts, the tables and the payload.  `note` ends the message about the symbol counts."""
     data = bytes(data)
     if len(data) < head.size:
         raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({head.size})")
-    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz, ncy,
-     *extra) = head.unpack_from(data, 0)
+    k = 1 + len(y_names)
+    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny,
+     *rest) = head.unpack_from(data, 0)
+    counts, extra = rest[:k], rest[k:]
     if s_magic != magic:
         raise ValueError(f"codec: bad magic {s_magic!r}")
     if ver != version:
@@ -258,34 +260,44 @@ def _parse(data, abi, compute_dtype, head, magic, version, make_header):
                          f"{compute_dtype!r}")
     if s_abi != abi:
         raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
-    h = make_header((N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky), extra)
-    if nz != h.nsym_z or ny != h.nsym_y:
-        raise ValueError("codec: symbol counts do not match the batch shape")
-    if ncz != num_chunks(nz, R) or ncy != num_chunks(ny, R):
+    h = header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky, *extra)
+    check(h)
+    nsyms = (h.nsym_z, *y_symbols(h))
+    if nz != nsyms[0] or any(len(y_names) * n != ny for n in nsyms[1:]):   # the streams of y hold equal shares of it
+        raise ValueError(f"codec: symbol counts do not match the batch shape{note}")
+    if any(c != num_chunks(n, R) for c, n in zip(counts, nsyms)):
         raise ValueError("codec: chunk counts do not match the symbol counts")
     off = head.size
-    if len(data) < off + 4 * (ncz + ncy):
+    if len(data) < off + 4 * sum(counts):
         raise ValueError("codec: buffer ends inside the chunk-length tables")
-    lens_z = np.frombuffer(data, dtype="<u4", count=ncz, offset=off)
-    lens_y = np.frombuffer(data, dtype="<u4", count=ncy, offset=off + 4 * ncz)
-    off += 4 * (ncz + ncy)
-    _check_lengths("z", lens_z, nz, R)
-    _check_lengths("y", lens_y, ny, R)
-    bz, by = int(lens_z.sum(dtype=np.uint64)), int(lens_y.sum(dtype=np.uint64))
-    if off + bz + by != len(data):
-        raise ValueError(f"codec: chunk lengths add up to {bz + by} payload bytes, the buffer holds {len(data) - off}")
-    return h, lens_z, lens_y, data[off:off + bz], data[off + bz:]
+    tables = []
+    for name, c, n in zip(("z", *y_names), counts, nsyms):
+        tables.append(np.frombuffer(data, dtype="<u4", count=c, offset=off))
+        off += 4 * c
+        _check_lengths(name, tables[-1], n, R)
+    sizes = [int(t.sum(dtype=np.uint64)) for t in tables]
+    if off + sum(sizes) != len(data):
+        raise ValueError(f"codec: chunk lengths add up to {sum(sizes)} payload bytes, the buffer holds {len(data) - off}")
+    ends = [off + sum(sizes[:i]) for i in range(k + 1)]
+    return (h, *tables, *(data[a:b] for a, b in zip(ends, ends[1:])))
+
+
+def fixed_bytes(h):
+    """The bytes of a container that do not depend on the symbols: header, length tables and the
+    256 bytes of lane states per chunk."""
+    return _fixed_bytes(_HEAD, h)
+
+
+def pack(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object from the header, the two chunk-length tables and the two payloads."""
+    return _pack(_HEAD, MAGIC, FORMAT_VERSION, _check_header, h, (lens_z, lens_y), (payload_z, payload_y))
 
 
 def parse(data, abi, compute_dtype):
     """(Header, lens_z, lens_y, payload_z, payload_y) of a container made by `pack`; `abi` and
     `compute_dtype` are the running build's ic_version() and the model's arithmetic, which the
     stream must match.  Raises ValueError on anything inconsistent; nothing is launched here."""
-    def make(common, _extra):
-        h = Header(*common)
-        _check_header(h)
-        return h
-    return _parse(data, abi, compute_dtype, _HEAD, MAGIC, FORMAT_VERSION, make)
+    return _parse(data, abi, compute_dtype, _HEAD, MAGIC, FORMAT_VERSION, Header, _check_header)
 
 
 def _check_image_header(h):
@@ -299,24 +311,20 @@ def _check_image_header(h):
 
 def image_fixed_bytes(h):
     """`fixed_bytes` of a per-image container."""
-    return fixed_bytes(h) + _IMAGE_HEAD.size - _HEAD.size
+    return _fixed_bytes(_IMAGE_HEAD, h)
 
 
 def pack_image(h, lens_z, lens_y, payload_z, payload_y):
     """One bytes object for one image from its ImageHeader, chunk-length tables and payloads."""
-    _check_image_header(h)
-    fields, body = _pack_body(h, lens_z, lens_y, payload_z, payload_y)
-    return b"".join((_IMAGE_HEAD.pack(IMAGE_MAGIC, IMAGE_FORMAT_VERSION, *fields, h.height, h.width),) + body)
+    return _pack(_IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, _check_image_header, h, (lens_z, lens_y),
+                 (payload_z, payload_y), (h.height, h.width))
 
 
 def parse_image(data, abi, compute_dtype):
     """(ImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_image`: the
     checks of `parse`, and those of the image size.  Nothing is launched here."""
-    def make(common, extra):
-        h = ImageHeader(*common, *extra)
-        _check_image_header(h)
-        return h
-    return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, make)
+    return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, ImageHeader,
+                  _check_image_header)
 
 
 # ---- checkerboard container "ICRC": y in two bitstreams, the anchors and the non-anchors
@@ -352,77 +360,27 @@ def _half_symbols(h):
     return tuple(h.N * C * checkerboard_count(hh, ww, p) for p in (0, 1))
 
 
+_HALVES = ("y anchor", "y non-anchor")
+
+
 def checkerboard_fixed_bytes(h):
     """`fixed_bytes` of a checkerboard container: three streams, each half of y chunked on its own."""
-    nc = num_chunks(h.nsym_z, h.R) + sum(num_chunks(n, h.R) for n in _half_symbols(h))
-    return _CKBD_HEAD.size + 4 * nc + CHUNK_HEAD * nc
+    return _fixed_bytes(_CKBD_HEAD, h, _half_symbols)
 
 
 def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn):
     """One bytes object from the header, the three chunk-length tables and the three payloads (z, the anchors
     of y, the non-anchors of y)."""
-    _check_checkerboard_header(h)
-    na, nn = _half_symbols(h)
-    tables, payloads = [], []
-    for name, lens, payload, nsym in (("z", lens_z, payload_z, h.nsym_z), ("y anchor", lens_ya, payload_ya, na),
-                                      ("y non-anchor", lens_yn, payload_yn, nn)):
-        lens, payload = np.ascontiguousarray(lens, dtype="<u4"), bytes(payload)
-        _check_lengths(name, lens, nsym, h.R)
-        if int(lens.sum(dtype=np.uint64)) != len(payload):
-            raise ValueError("codec: chunk lengths do not add up to the payload")
-        tables.append(lens.tobytes())
-        payloads.append(payload)
-    head = _CKBD_HEAD.pack(CKBD_MAGIC, CKBD_FORMAT_VERSION, COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H,
-                           h.W, h.latent_channels, h.hyper_channels, h.L, h.scale_min, h.scale_max, h.R, h.kmax_z,
-                           h.kmax_y, h.nsym_z, h.nsym_y, *(len(t) // 4 for t in tables))
-    return b"".join([head] + tables + payloads)
+    return _pack(_CKBD_HEAD, CKBD_MAGIC, CKBD_FORMAT_VERSION, _check_checkerboard_header, h, (lens_z, lens_ya, lens_yn),
+                 (payload_z, payload_ya, payload_yn), (), _HALVES, _half_symbols)
 
 
 def parse_checkerboard(data, abi, compute_dtype):
     """(Header, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
     `pack_checkerboard`, with the checks of `parse`.  Raises ValueError on anything inconsistent; nothing is
     launched here."""
-    data = bytes(data)
-    if len(data) < _CKBD_HEAD.size:
-        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({_CKBD_HEAD.size})")
-    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny, ncz, nca,
-     ncn) = _CKBD_HEAD.unpack_from(data, 0)
-    if s_magic != CKBD_MAGIC:
-        raise ValueError(f"codec: bad magic {s_magic!r}")
-    if ver != CKBD_FORMAT_VERSION:
-        raise ValueError(f"codec: format version {ver}, this build reads {CKBD_FORMAT_VERSION}")
-    if dt >= len(COMPUTE_DTYPES):
-        raise ValueError(f"codec: unknown arithmetic tag {dt}")
-    if COMPUTE_DTYPES[dt] != compute_dtype:
-        raise ValueError(f"codec: stream coded with COMPUTE_DTYPE {COMPUTE_DTYPES[dt]!r}, the model runs "
-                         f"{compute_dtype!r}")
-    if s_abi != abi:
-        raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
-    h = Header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky)
-    _check_checkerboard_header(h)
-    na, nn = _half_symbols(h)
-    if nz != h.nsym_z or ny != h.nsym_y or 2 * na != ny or 2 * nn != ny:
-        raise ValueError("codec: symbol counts do not match the batch shape (y in two equal halves)")
-    counts, nsyms = (ncz, nca, ncn), (nz, na, nn)
-    if any(c != num_chunks(n, R) for c, n in zip(counts, nsyms)):
-        raise ValueError("codec: chunk counts do not match the symbol counts")
-    off = _CKBD_HEAD.size
-    if len(data) < off + 4 * sum(counts):
-        raise ValueError("codec: buffer ends inside the chunk-length tables")
-    tables = []
-    for name, c, n in zip(("z", "y anchor", "y non-anchor"), counts, nsyms):
-        lens = np.frombuffer(data, dtype="<u4", count=c, offset=off)
-        off += 4 * c
-        _check_lengths(name, lens, n, R)
-        tables.append(lens)
-    sizes = [int(t.sum(dtype=np.uint64)) for t in tables]
-    if off + sum(sizes) != len(data):
-        raise ValueError(f"codec: chunk lengths add up to {sum(sizes)} payload bytes, the buffer holds {len(data) - off}")
-    payloads = []
-    for s in sizes:
-        payloads.append(data[off:off + s])
-        off += s
-    return (h, *tables, *payloads)
+    return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, CKBD_FORMAT_VERSION, Header,
+                  _check_checkerboard_header, _HALVES, _half_symbols, " (y in two equal halves)")
 
 
 def split_packed_seg(packed, nseg, seg_len, R):
@@ -446,13 +404,7 @@ def join_packed_seg(parts):
 
 def split_packed(packed, nsym, R):
     """(lengths, payload bytes) of the device coder's output buffer [lengths][payload][padding]."""
-    packed = np.asarray(packed, dtype=np.uint8)
-    nc = num_chunks(nsym, R)
-    lens = packed[:4 * nc].view("<u4").copy()
-    total = int(lens.sum(dtype=np.uint64))
-    if 4 * nc + total > packed.size:
-        raise RuntimeError("codec: the coder reported more bytes than its buffer holds")
-    return lens, packed[4 * nc:4 * nc + total].tobytes()
+    return split_packed_seg(packed, 1, nsym, R)[0]
 
 
 def join_packed(lens, payload):

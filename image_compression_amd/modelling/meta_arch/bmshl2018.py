@@ -179,15 +179,22 @@ class Compressor2018(nn.Module):
             z_ce = _StreamEdge.apply(z_ce, side)
             y_ce = _StreamEdge.apply(y_ce, side)
         else:
-            z = self.prior_analysis(AbsFn.apply(y))
+            # the serial step of every model, its differences in _hyper_input, _prior and _forward_y
+            z = self.prior_analysis(self._hyper_input(y))
             z_tilde, _z_probs, z_ce = self.entropy_model(z)
-            sigma = self.prior_synthesis(z_tilde)
-            y_tilde, y_probs = self.conditional_model(y, sigma)
+            y_tilde, y_probs = self._forward_y(y, *self._prior(z_tilde))
             y_ce = self.conditional_model._ce_loss(y_probs)
-            x_tilde = self.synthesis_transform(y_tilde)
-            x_tilde = LowerBound.apply(UpperBound.apply(x_tilde, 1.), 0.)
+            x_tilde = self._reconstruct(y_tilde)
             dist = self.distortion_loss(x, x_tilde)
         return x_tilde.detach(), self._losses(z_ce, y_ce, dist, num_pixels)
+
+    def _forward_y(self, y, sigma, mean):
+        """(y_tilde, p_y) of the forward from y and `_prior`'s (sigma, mean): how y is quantised and scored."""
+        return self.conditional_model(y, sigma)
+
+    def _reconstruct(self, y_hat):
+        """g_s and the clamp to [0, 1]."""
+        return LowerBound.apply(UpperBound.apply(self.synthesis_transform(y_hat), 1.), 0.)
 
     def _losses(self, z_ce, y_ce, dist, num_pixels):
         total_dist = sum(dist.values())
@@ -212,8 +219,11 @@ class Compressor2018(nn.Module):
             raise RuntimeError("compress / decompress run in eval mode only: call model.eval() first")
         self._clear_reparameterised()
 
-    # The three points where a model with another hyperprior differs (MeanScaleCompressor2018): what h_a
-    # reads, what h_s gives, and the conditional-kind byte that says so in the container.
+    # Where a model with another hyperprior or another way of coding y differs (MeanScaleCompressor2018,
+    # CheckerboardCompressor2018): what h_a reads (_hyper_input), what h_s gives (_prior), the conditional-kind byte that
+    # says so in the container (_stream_kind), how the forward quantises and scores y (_forward_y, above), how y becomes
+    # streams and comes back (_encode_y / _decode_y), and the container of a batch with the checks in front of it
+    # (_pack / _parse, _codable_batch).
     def _hyper_input(self, y):
         return AbsFn.apply(y)
 
@@ -224,50 +234,95 @@ class Compressor2018(nn.Module):
     def _stream_kind(self):
         return self.conditional_model.KIND
 
+    def _encode_y(self, y, prior, steps_per_chunk):
+        """(kmax_y, the streams [(payload, chunk lengths)] of y) under `_prior`'s (sigma, mean)."""
+        sigma, mean = prior
+        y_sym, ky = self._symbols(y, mean)
+        return ky, [self.conditional_model.encode_symbols(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)]
+
+    def _decode_y(self, h, streams, prior):
+        """y_hat from the parsed header, the streams [(payload, chunk lengths)] of y and `_prior`'s (sigma, mean)."""
+        (py, ly), = streams
+        sigma, mean = prior
+        return self.conditional_model.decompress(py, sigma, ly, h.kmax_y, h.R, mean=mean)
+
+    _pack, _parse = staticmethod(_codec.pack), staticmethod(_codec.parse)
+
+    def _codable_batch(self):
+        self._codable()
+
+    # ---- what compress, decompress and their per-image forms share
+    def _build_id(self):
+        """(ic_version(), COMPUTE_DTYPE): what a stream must have been coded by, as the parsers take them."""
+        return int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32")
+
+    @staticmethod
+    def _symbols(t, mean=None, each=False):
+        """(int32 symbols, kmax) of t, about `mean` if there is one; `each`: image by image ([kmax of image n])."""
+        if not each:
+            return symbolize(t) if mean is None else symbolize_mean(t, mean)
+        try:
+            return symbolize_seg(t) if mean is None else symbolize_mean_seg(t, mean)
+        except ValueError as e:
+            raise ValueError(f"compress_each: {e}") from None
+
+    def _analyse(self, x, each=False):
+        """(y, z, symbols of z, kmax_z, `_prior`): g_a, h_a, and sigma (and the mean) from the integers the decoder
+        will hold, in the layout it will hold them in; `each`: one image at a time, as that decoder computes them."""
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(self._hyper_input(y))
+        z_sym, kz = self._symbols(z, each=each)
+        z_hat = symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape))
+        return y, z, z_sym, kz, (self._prior_each if each else self._prior)(z_hat)
+
+    def _header(self, N, H, W, y, z, steps_per_chunk, kz, ky, size=None):
+        """The Header of a batch's stream, or with `size` = (h, w) the ImageHeader of one image's."""
+        cm = self.conditional_model
+        abi, dtype = self._build_id()
+        h = (_codec.Header if size is None else _codec.ImageHeader)(
+            N, H, W, y.shape[1], z.shape[1], self._stream_kind(), dtype, abi, cm.num_scales, cm.scale_min, cm.scale_max,
+            int(steps_per_chunk), kz, ky, *(size or ()))
+        if tuple(z.shape[1:]) != h.z_shape[1:] or tuple(y.shape[1:]) != h.y_shape[1:]:
+            who, what = ("compress", "image") if size is None else ("compress_each", "padded image")
+            raise ValueError(f"{who}: latents {tuple(y.shape)} / {tuple(z.shape)} are not the {what} size over "
+                             f"{_codec.Y_DOWN} / {_codec.Z_DOWN}")
+        return h
+
+    def _check_stream(self, h, who, stream="the stream"):
+        em, cm = self.entropy_model, self.conditional_model
+        if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
+            raise ValueError(f"{who}: {stream} was coded by a different model (conditional kind / channels)")
+        if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
+            raise ValueError(f"{who}: {stream} was coded with a different scale table")
+
     @torch.no_grad()
     def compress(self, x, steps_per_chunk=1024):
         """x (N, 3, H, W) in [0, 1], H and W multiples of 64 -> one bytes object for the batch."""
-        self._codable()
+        self._codable_batch()
         if x.dim() != 4 or x.shape[2] % _codec.Z_DOWN or x.shape[3] % _codec.Z_DOWN:
             raise ValueError(f"compress: image size {tuple(x.shape)} must be (N, C, H, W) with H and W "
                              f"multiples of {_codec.Z_DOWN}")
-        em, cm = self.entropy_model, self.conditional_model
         N, _, H, W = x.shape
-        y = self.analysis_transform(x)
-        z = self.prior_analysis(self._hyper_input(y))
-        z_sym, kz = symbolize(z)
-        # sigma (and the mean) from the integers the decoder will hold, in the layout it will hold them in
-        sigma, mean = self._prior(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
-        pz, lz = em.encode_symbols(z_sym, kz, steps_per_chunk)
-        y_sym, ky = symbolize(y) if mean is None else symbolize_mean(y, mean)
-        py, ly = cm.encode_symbols(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)
-        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], self._stream_kind(), getattr(self, "compute_dtype", "fp32"),
-                          int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max, int(steps_per_chunk),
-                          kz, ky)
-        if tuple(z.shape) != h.z_shape or tuple(y.shape) != h.y_shape:
-            raise ValueError(f"compress: latents {tuple(y.shape)} / {tuple(z.shape)} are not the image size over "
-                             f"{_codec.Y_DOWN} / {_codec.Z_DOWN}")
-        return _codec.pack(h, lz, ly, pz, py)
+        y, z, z_sym, kz, prior = self._analyse(x)
+        pz, lz = self.entropy_model.encode_symbols(z_sym, kz, steps_per_chunk)
+        ky, streams = self._encode_y(y, prior, steps_per_chunk)
+        h = self._header(N, H, W, y, z, steps_per_chunk, kz, ky)
+        return self._pack(h, lz, *(l for _, l in streams), pz, *(p for p, _ in streams))
 
     @torch.no_grad()
     def decompress(self, data):
         """bytes from `compress` (same weights, build, COMPUTE_DTYPE, device type and batch shape) ->
         x_hat (N, 3, H, W), the eval forward's reconstruction."""
-        self._codable()
-        em, cm = self.entropy_model, self.conditional_model
-        h, lz, ly, pz, py = _codec.parse(data, int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32"))
-        if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
-            raise ValueError("decompress: the stream was coded by a different model (conditional kind / channels)")
-        if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
-            raise ValueError("decompress: the stream was coded with a different scale table")
-        z_hat = em.decompress(pz, h.z_shape, lz, h.kmax_z, h.R)
-        sigma, mean = self._prior(z_hat)
-        if tuple(sigma.shape) != h.y_shape:
-            raise ValueError(f"decompress: the model's sigma {tuple(sigma.shape)} is not the stream's latent shape "
+        self._codable_batch()
+        h, *rest = self._parse(data, *self._build_id())
+        lens, payloads = rest[:len(rest) // 2], rest[len(rest) // 2:]
+        self._check_stream(h, "decompress")
+        z_hat = self.entropy_model.decompress(payloads[0], h.z_shape, lens[0], h.kmax_z, h.R)
+        prior = self._prior(z_hat)
+        if any(t is not None and tuple(t.shape) != h.y_shape for t in prior):
+            raise ValueError(f"decompress: the model's sigma {tuple(prior[0].shape)} is not the stream's latent shape "
                              f"{h.y_shape}")
-        y_hat = cm.decompress(py, sigma, ly, h.kmax_y, h.R, mean=mean)
-        x_hat = self.synthesis_transform(y_hat)
-        return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)
+        return self._reconstruct(self._decode_y(h, list(zip(payloads[1:], lens[1:])), prior))
 
     # ---- per-image streams: any image size, every image its own self-contained stream (container
     # "ICRP", codec.py).  The one rule that makes stream n decodable alone: h_s runs one image at a
@@ -297,28 +352,12 @@ class Compressor2018(nn.Module):
         if (H, W) != (h, w):
             _lib.require_device(x)
             x = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
-        y = self.analysis_transform(x)
-        z = self.prior_analysis(self._hyper_input(y))
-        try:
-            z_sym, kz = symbolize_seg(z)
-            # sigma (and the mean) from the integers the decoder will hold, one image at a time as the decoder
-            # computes them
-            sigma, mean = self._prior_each(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
-            y_sym, ky = symbolize_seg(y) if mean is None else symbolize_mean_seg(y, mean)
-        except ValueError as e:
-            raise ValueError(f"compress_each: {e}") from None
+        y, z, z_sym, kz, (sigma, mean) = self._analyse(x, each=True)
+        y_sym, ky = self._symbols(y, mean, each=True)
         sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
         sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)
-        out = []
-        for n in range(N):
-            hd = _codec.ImageHeader(1, H, W, y.shape[1], z.shape[1], self._stream_kind(),
-                                    getattr(self, "compute_dtype", "fp32"), int(_lib.load().ic_version()), cm.num_scales,
-                                    cm.scale_min, cm.scale_max, int(steps_per_chunk), kz[n], ky[n], h, w)
-            if tuple(z.shape[1:]) != hd.z_shape[1:] or tuple(y.shape[1:]) != hd.y_shape[1:]:
-                raise ValueError(f"compress_each: latents {tuple(y.shape)} / {tuple(z.shape)} are not the padded image "
-                                 f"size over {_codec.Y_DOWN} / {_codec.Z_DOWN}")
-            out.append(_codec.pack_image(hd, sz[n][1], sy[n][1], sz[n][0], sy[n][0]))
-        return out
+        return [_codec.pack_image(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w)),
+                                  sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
 
     @torch.no_grad()
     def decompress_each(self, streams):
@@ -327,15 +366,10 @@ class Compressor2018(nn.Module):
         size and chunk size are decoded by the same launches and pass g_s as one batch."""
         self._codable_each()
         em, cm = self.entropy_model, self.conditional_model
-        abi, dt = int(_lib.load().ic_version()), getattr(self, "compute_dtype", "fp32")
-        parsed = [_codec.parse_image(d, abi, dt) for d in streams]   # everything is validated before any launch
+        parsed = [_codec.parse_image(d, *self._build_id()) for d in streams]   # everything is validated before any launch
         groups = {}
         for m, (h, *_rest) in enumerate(parsed):
-            if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
-                raise ValueError(f"decompress_each: stream {m} was coded by a different model (conditional kind / "
-                                 "channels)")
-            if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
-                raise ValueError(f"decompress_each: stream {m} was coded with a different scale table")
+            self._check_stream(h, "decompress_each", f"stream {m}")
             groups.setdefault((h.H, h.W, h.latent_channels, h.R), []).append(m)
         out = [None] * len(parsed)
         for (H, W, _cy, R), idx in groups.items():
@@ -348,16 +382,17 @@ class Compressor2018(nn.Module):
                                  f"shape {hs[0].y_shape}")
             y_hat = cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
                                       [h.kmax_y for h in hs], R, mean=mean)
-            x_hat = self.synthesis_transform(y_hat)
             sizes = {(h.height, h.width) for h in hs}
             if sizes == {(H, W)}:
-                x_hat = LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.).contiguous()
-                imgs = [x_hat[k:k + 1] for k in range(len(idx))]
-            elif len(sizes) == 1:
-                x_hat = _lib.stream_ops().crop_clamp(x_hat, *next(iter(sizes)))
+                x_hat = self._reconstruct(y_hat).contiguous()
                 imgs = [x_hat[k:k + 1] for k in range(len(idx))]
             else:
-                imgs = [_lib.stream_ops().crop_clamp(x_hat[k:k + 1], h.height, h.width) for k, h in enumerate(hs)]
+                x_hat = self.synthesis_transform(y_hat)
+                if len(sizes) == 1:
+                    x_hat = _lib.stream_ops().crop_clamp(x_hat, *next(iter(sizes)))
+                    imgs = [x_hat[k:k + 1] for k in range(len(idx))]
+                else:
+                    imgs = [_lib.stream_ops().crop_clamp(x_hat[k:k + 1], h.height, h.width) for k, h in enumerate(hs)]
             for m, img in zip(idx, imgs):
                 out[m] = img
         return out

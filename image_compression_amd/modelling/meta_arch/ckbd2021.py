@@ -27,13 +27,11 @@ and the convs are deterministic for a given shape, arithmetic and build."""
 import torch
 import torch.nn as nn
 
-from ... import _lib
 from ... import codec as _codec
-from ... import noise as _noise
 from ...functional import conditional_likelihood
 from ..blocks.entropy_model import (_decode, _encode, add_mean, center_round, ckbd_gather, ckbd_input, ckbd_params,
-                                    ckbd_scatter, symbolize, symbolize_mean, symbols_as_tensor)
-from ..layers import Conv2d, LowerBound, UpperBound
+                                    ckbd_scatter, symbolize_mean)
+from ..layers import Conv2d
 from .build import META_ARCH_REGISTRY
 from .mshp2018 import MeanScaleCompressor2018
 
@@ -68,80 +66,37 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         _, y_anchor = center_round(y, mu_h.expand_as(y))
         return self._context(y_anchor, sigma_h.expand_as(y), mu_h.expand_as(y))
 
-    def _forward(self, x):
+    def _forward_y(self, y, sigma_h, mu_h):
         cm = self.conditional_model
-        if self.training:
-            _noise.begin_step(x.device)  # fresh Philox counters for this step
-        elif float(cm.bin) != 1.0:
-            raise NotImplementedError(f"the eval forward rounds the residual to integers: BIN must be 1, got {cm.bin}")
-        self._reparameterise_gdn(x)
-        N, _, H, W = x.shape
-        y = self.analysis_transform(x)
-        z = self.prior_analysis(y)
-        z_tilde, _z_probs, z_ce = self.entropy_model(z)
-        sigma_h, mu_h = self._prior(z_tilde)
         if self.training:
             y_tilde = cm.quantize(y)
             sigma, mu = self._context(y_tilde, sigma_h.expand_as(y), mu_h.expand_as(y))
-            y_probs = conditional_likelihood(y_tilde, sigma, mu, cm.KIND, cm.bin)
-        else:
-            sigma, mu = self._eval_params(y, sigma_h, mu_h)
-            r, y_tilde = center_round(y, mu)   # at the anchors mu is mu_h bit for bit: one call serves both halves
-            y_probs = cm.likelihood(r, sigma)
-        y_ce = cm._ce_loss(y_probs)
-        x_tilde = self.synthesis_transform(y_tilde)
-        x_tilde = LowerBound.apply(UpperBound.apply(x_tilde, 1.), 0.)
-        dist = self.distortion_loss(x, x_tilde)
-        return x_tilde.detach(), self._losses(z_ce, y_ce, dist, N * H * W)
+            return y_tilde, conditional_likelihood(y_tilde, sigma, mu, cm.KIND, cm.bin)
+        sigma, mu = self._eval_params(y, sigma_h, mu_h)
+        r, y_tilde = center_round(y, mu)   # at the anchors mu is mu_h bit for bit: one call serves both halves
+        return y_tilde, cm.likelihood(r, sigma)
 
     # ---- bitstreams: container "ICRC" (codec.py), y as two streams -- the anchors, then the non-anchors
-    @torch.no_grad()
-    def compress(self, x, steps_per_chunk=1024):
-        """x (N, 3, H, W) in [0, 1], H and W multiples of 64 -> one bytes object for the batch."""
-        self._codable_each()
-        if x.dim() != 4 or x.shape[2] % _codec.Z_DOWN or x.shape[3] % _codec.Z_DOWN:
-            raise ValueError(f"compress: image size {tuple(x.shape)} must be (N, C, H, W) with H and W "
-                             f"multiples of {_codec.Z_DOWN}")
-        em, cm = self.entropy_model, self.conditional_model
-        N, _, H, W = x.shape
-        y = self.analysis_transform(x)
-        z = self.prior_analysis(self._hyper_input(y))
-        z_sym, kz = symbolize(z)
-        # (sigma_h, mu_h) from the integers the decoder will hold, then the context of the anchors as it decodes them
-        sigma_h, mu_h = self._prior(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
-        pz, lz = em.encode_symbols(z_sym, kz, steps_per_chunk)
-        sigma, mu = self._eval_params(y, sigma_h, mu_h)
-        y_sym, ky = symbolize_mean(y, mu)       # one K and one table set for both halves
-        h = _codec.Header(N, H, W, y.shape[1], z.shape[1], self._stream_kind(), getattr(self, "compute_dtype", "fp32"),
-                          int(_lib.load().ic_version()), cm.num_scales, cm.scale_min, cm.scale_max, int(steps_per_chunk),
-                          kz, ky)
-        if tuple(z.shape) != h.z_shape or tuple(y.shape) != h.y_shape:
-            raise ValueError(f"compress: latents {tuple(y.shape)} / {tuple(z.shape)} are not the image size over "
-                             f"{_codec.Y_DOWN} / {_codec.Z_DOWN}")
-        rows, tables = cm.scale_rows(sigma), cm.tables(ky, y.device)
-        halves = [_encode(ckbd_gather(y_sym, h.y_shape, p), ckbd_gather(rows, h.y_shape, p), 0, tables, steps_per_chunk)
-                  for p in (0, 1)]
-        (pa, la), (pn, ln) = halves
-        return _codec.pack_checkerboard(h, lz, la, ln, pz, pa, pn)
+    _pack, _parse = staticmethod(_codec.pack_checkerboard), staticmethod(_codec.parse_checkerboard)
 
-    @torch.no_grad()
-    def decompress(self, data):
-        """bytes from `compress` (same weights, build, COMPUTE_DTYPE, device type and batch shape) ->
-        x_hat (N, 3, H, W), the eval forward's reconstruction.  Two passes: the anchors from the hyperprior, then the
-        non-anchors from the hyperprior and the decoded anchors."""
-        self._codable_each()
-        em, cm = self.entropy_model, self.conditional_model
-        h, lz, la, ln, pz, pa, pn = _codec.parse_checkerboard(data, int(_lib.load().ic_version()),
-                                                              getattr(self, "compute_dtype", "fp32"))
-        if h.kind != self._stream_kind() or h.hyper_channels != em.channels:
-            raise ValueError("decompress: the stream was coded by a different model (conditional kind / channels)")
-        if (h.L, h.scale_min, h.scale_max) != (cm.num_scales, cm.scale_min, cm.scale_max):
-            raise ValueError("decompress: the stream was coded with a different scale table")
-        z_hat = em.decompress(pz, h.z_shape, lz, h.kmax_z, h.R)
-        sigma_h, mu_h = self._prior(z_hat)
-        if tuple(sigma_h.shape) != h.y_shape or tuple(mu_h.shape) != h.y_shape:
-            raise ValueError(f"decompress: the model's sigma {tuple(sigma_h.shape)} is not the stream's latent shape "
-                             f"{h.y_shape}")
+    def _codable_batch(self):
+        self._codable_each()    # BIN == 1, before anything is computed
+
+    def _encode_y(self, y, prior, steps_per_chunk):
+        """The context of the anchors as the decoder will decode them, then each half of y as a stream of its own."""
+        cm, shape = self.conditional_model, tuple(y.shape)
+        sigma, mu = self._eval_params(y, *prior)
+        y_sym, ky = symbolize_mean(y, mu)       # one K and one table set for both halves
+        rows, tables = cm.scale_rows(sigma), cm.tables(ky, y.device)
+        return ky, [_encode(ckbd_gather(y_sym, shape, p), ckbd_gather(rows, shape, p), 0, tables, steps_per_chunk)
+                    for p in (0, 1)]
+
+    def _decode_y(self, h, streams, prior):
+        """Two passes: the anchors from the hyperprior, then the non-anchors from the hyperprior and the decoded
+        anchors."""
+        cm = self.conditional_model
+        (pa, la), (pn, ln) = streams
+        sigma_h, mu_h = prior
         dev, half = sigma_h.device, h.nsym_y // 2
         tables = cm.tables(h.kmax_y, dev)
         flat = torch.zeros(h.nsym_y, dtype=torch.float32, device=dev)
@@ -152,8 +107,7 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         # pass two: the non-anchors, under the parameters the decoded anchors give them
         rows = ckbd_gather(cm.scale_rows(sigma), h.y_shape, 1)
         ckbd_scatter(_decode(pn, ln, half, rows, 0, tables, h.R, dev), flat, h.y_shape, 1)
-        x_hat = self.synthesis_transform(add_mean(flat, mu))
-        return LowerBound.apply(UpperBound.apply(x_hat, 1.), 0.)
+        return add_mean(flat, mu)
 
     # Per-image streams need the context convs run one image at a time on both sides, as h_s is (`_prior_each`): not built.
     def compress_each(self, x, steps_per_chunk=1024):

@@ -20,9 +20,8 @@ import torch
 import torch.nn as nn
 
 from ... import codec as _codec
-from ... import noise as _noise
 from ..blocks.entropy_model import center_round
-from ..layers import ConvTranspose2d, LowerBound, UpperBound
+from ..layers import ConvTranspose2d
 from .bmshl2018 import Compressor2018
 from .build import META_ARCH_REGISTRY
 
@@ -64,30 +63,19 @@ class MeanScaleCompressor2018(Compressor2018):
         p_y = conditional(y, sigma, mu); the Philox draws in the same order (z, then y).
         Eval: inference only -- y_hat = rint(y - mu) + mu, p_y the pmf of the residual at mean 0 (what the
         coder's tables are built from), the whole forward under no_grad: its outputs carry no grad."""
+        if self.concurrent_hyperprior:   # Compressor2018's side-stream branch is the scale-only step
+            raise NotImplementedError("the mean-scale hyperprior runs serially: concurrent_hyperprior must stay False")
         if self.training:
             return super().forward(x)
+        cm = self.conditional_model
+        if float(cm.bin) != 1.0:   # in front of any launch
+            raise NotImplementedError(f"the eval forward rounds the residual to integers: BIN must be 1, got {cm.bin}")
         with torch.no_grad():
             return super().forward(x)
 
-    def _forward(self, x):
+    def _forward_y(self, y, sigma, mu):
         cm = self.conditional_model
         if self.training:
-            _noise.begin_step(x.device)  # fresh Philox counters for this step
-        elif float(cm.bin) != 1.0:
-            raise NotImplementedError(f"the eval forward rounds the residual to integers: BIN must be 1, got {cm.bin}")
-        self._reparameterise_gdn(x)
-        N, _, H, W = x.shape
-        y = self.analysis_transform(x)
-        z = self.prior_analysis(y)
-        z_tilde, _z_probs, z_ce = self.entropy_model(z)
-        sigma, mu = self._prior(z_tilde)
-        if self.training:
-            y_tilde, y_probs = cm(y, sigma, mu)
-        else:
-            r, y_tilde = center_round(y, mu.expand_as(y))
-            y_probs = cm.likelihood(r, sigma)
-        y_ce = cm._ce_loss(y_probs)
-        x_tilde = self.synthesis_transform(y_tilde)
-        x_tilde = LowerBound.apply(UpperBound.apply(x_tilde, 1.), 0.)
-        dist = self.distortion_loss(x, x_tilde)
-        return x_tilde.detach(), self._losses(z_ce, y_ce, dist, N * H * W)
+            return cm(y, sigma, mu)
+        r, y_tilde = center_round(y, mu.expand_as(y))
+        return y_tilde, cm.likelihood(r, sigma)

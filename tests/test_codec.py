@@ -3,6 +3,7 @@ image_compression_amd/codec.py (64-lane interleaving, word order, chunking, flus
 pack / parse with its validation, and the registration of the coder's ops.  No GPU: the kernels are
 held to this reference, byte for byte, in tests/test_codec_gpu.py."""
 import dataclasses
+import hashlib
 import struct
 
 import numpy as np
@@ -197,6 +198,43 @@ def test_parse_rejects_inconsistent_buffers():
         codec.pack(dataclasses.replace(h, H=192), lz, ly, pz, py)
     with pytest.raises(ValueError, match="multiple"):
         codec.pack(dataclasses.replace(h, W=96), lz, ly, pz, py)
+
+
+def _pinned_stream(codec, nsym, R, salt):
+    """Chunk lengths within their bounds and payload bytes from integer arithmetic alone."""
+    per = 64 * R
+    lens = np.asarray([256 + 2 * ((7 * c + salt) % (min(per, nsym - c * per) + 1)) for c in range(codec.num_chunks(nsym, R))],
+                      dtype=np.uint32)
+    return lens, bytes((37 * i + salt) & 255 for i in range(int(lens.sum())))
+
+
+def test_container_bytes_are_pinned():
+    """The three containers byte for byte: SHA-256 of the packed bytes of fixed inputs, the digests computed with the
+    codec.py of the commit before the three packers and parsers were folded into one framing routine.  R = 2, every
+    stream with more than one chunk and a short last one; the per-image size is no multiple of 64."""
+    from image_compression_amd import codec
+    common = dict(latent_channels=3, compute_dtype="fp32_split", abi=4, L=64, scale_min=0.11, scale_max=256.0, R=2,
+                  kmax_z=3, kmax_y=40)
+    batch = dict(N=2, H=128, W=192, hyper_channels=11)
+    cases = (
+        (codec.Header(kind=0, **batch, **common), codec.pack, codec.parse, None,
+         "b66d450ec4ddf54262cda04db6e0475a43b4bc89660d448c695493e76b1e504c"),
+        (codec.ImageHeader(N=1, H=128, W=192, hyper_channels=23, kind=2, height=100, width=150, **common),
+         codec.pack_image, codec.parse_image, None, "3ddd852a15fec057813c7619cbd45ae8ed1767b8308643cfccfbf449d9c9f1af"),
+        (codec.Header(kind=2, **batch, **common), codec.pack_checkerboard, codec.parse_checkerboard, 2,
+         "a0850377951b158bd35b9927bb9e19acedc5f961d18c1dfcae0188a6e61eb384"),
+    )
+    for h, pack, parse, halves, digest in cases:
+        nsyms = [h.nsym_z] + ([h.nsym_y] if halves is None else [h.nsym_y // halves] * halves)
+        streams = [_pinned_stream(codec, n, h.R, salt) for salt, n in enumerate(nsyms, 1)]
+        lens, payloads = [s[0] for s in streams], [s[1] for s in streams]
+        for l, n in zip(lens, nsyms):
+            assert len(l) > 1 and n % (64 * h.R), "one chunk only, or a full last chunk"
+        data = pack(h, *lens, *payloads)
+        assert hashlib.sha256(data).hexdigest() == digest, pack.__name__
+        h2, *rest = parse(data, abi=4, compute_dtype="fp32_split")
+        assert h2 == h and type(h2) is type(h)
+        assert all(np.array_equal(a, b) for a, b in zip(rest[:len(lens)], lens)) and rest[len(lens):] == payloads
 
 
 def test_scale_table_is_the_documented_one():

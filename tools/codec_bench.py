@@ -65,7 +65,7 @@ def each_bench(args, model, cfg):
     """--each N: the loop over single-image batches against compress_each / decompress_each."""
     from image_compression_amd import _lib, codec
     from image_compression_amd import functional as F
-    from image_compression_amd.modelling.blocks.entropy_model import symbolize_mean_seg, symbolize_seg, table_pool
+    from image_compression_amd.modelling.blocks.entropy_model import table_pool
     N, H, W, reps = args.each, args.height, args.width, args.reps
     g = torch.Generator(device="cuda").manual_seed(5)
     x = torch.rand(N, 3, H, W, device="cuda", generator=g)
@@ -94,13 +94,10 @@ def each_bench(args, model, cfg):
         t_odd_d = _wall(lambda: model.decompress_each(odd), reps)
         # the coder ops alone, on the latents of these images: N launches of the whole-tensor kernels against
         # one launch of the segmented ones
-        y = model.analysis_transform(x)
-        z = model.prior_analysis(model._hyper_input(y))
-        z_sym, kz = symbolize_seg(z)
+        y, z, z_sym, kz, (sigma, mean) = model._analyse(x, each=True)
         z_hat = z_sym.float().view(N, *z.shape[2:], z.shape[1]).movedim(-1, 1)
-        sigma, mean = model._prior_each(z_hat)
         sigma = sigma.expand_as(y)
-        y_sym, ky = symbolize_seg(y) if mean is None else symbolize_mean_seg(y, mean)
+        y_sym, ky = model._symbols(y, mean, each=True)
         rows = cm.scale_rows(sigma)
         ny, nz = y_sym.numel() // N, z_sym.numel() // N
         y_l = y.movedim(1, -1).contiguous()
@@ -178,7 +175,6 @@ def main():
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
-    from image_compression_amd.modelling.blocks.entropy_model import symbolize, symbolize_mean
     if args.compare:
         _emit(compare_bench(args), args.out)
         return
@@ -214,12 +210,9 @@ def main():
             return
         # the coder's ops alone, on this image's latents
         h = codec.parse(data, int(_lib.load().ic_version()), cfg.MODEL.COMPUTE_DTYPE)[0]
-        y = model.analysis_transform(x)
-        z = model.prior_analysis(model._hyper_input(y))
-        z_sym, kz = symbolize(z)
-        sigma, mean = model._prior(z_sym.float().view(1, *z.shape[2:], z.shape[1]).movedim(-1, 1))
+        y, z, z_sym, kz, (sigma, mean) = model._analyse(x)
         sigma = sigma.expand_as(y)
-        y_sym, ky = symbolize(y) if mean is None else symbolize_mean(y, mean)
+        y_sym, ky = model._symbols(y, mean)
         sig_l = sigma.movedim(1, -1).contiguous()
         if mean is None:
             sym_y = lambda: ops.symbolize(y.movedim(1, -1).contiguous())
