@@ -222,34 +222,21 @@ _lib = None
 _load_error = None
 TORCH_OPS_PATH = os.path.join(os.path.dirname(LIB_PATH), "libimgcomp_torch.so")
 _ops = None
-_codec_ops = None
 
 
-def codec_ops():
-    """torch.ops.imgcomp_codec (the entropy coder's ops, registered by the same library as ops())."""
-    global _codec_ops
-    if _codec_ops is None:
+def _namespace(name, doc):
+    """An accessor of torch.ops.<name>, one of the namespaces the library of ops() registers besides imgcomp."""
+    def get():
         ops()
-        _codec_ops = torch.ops.imgcomp_codec
-    return _codec_ops
+        return getattr(torch.ops, name)
+    get.__name__, get.__doc__ = name[len("imgcomp_"):] + "_ops", f"torch.ops.{name} ({doc})."
+    return get
 
 
-def stream_ops():
-    """torch.ops.imgcomp_stream (the segmented coder and the image borders of the per-image streams)."""
-    ops()
-    return torch.ops.imgcomp_stream
-
-
-def mean_ops():
-    """torch.ops.imgcomp_mean (the mean-scale hyperprior's symbolizers, quantiser and reconstruction)."""
-    ops()
-    return torch.ops.imgcomp_mean
-
-
-def ckbd_ops():
-    """torch.ops.imgcomp_ckbd (the checkerboard context model's masks, parameters and halves)."""
-    ops()
-    return torch.ops.imgcomp_ckbd
+codec_ops = _namespace("imgcomp_codec", "the entropy coder's ops")
+stream_ops = _namespace("imgcomp_stream", "the segmented coder and the image borders of the per-image streams")
+mean_ops = _namespace("imgcomp_mean", "the mean-scale hyperprior's symbolizers, quantiser and reconstruction")
+ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, parameters and halves")
 
 
 def ops():

@@ -61,433 +61,326 @@ void check_rc(int rc, const char* what) {
 
 float* opt_ptr(const c10::optional<Tensor>& t) { return t.has_value() && t->defined() ? t->data_ptr<float>() : nullptr; }
 
-// ---------------------------------------------------------------- conv2d
-Tensor conv2d_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride, int64_t pad,
-                  int64_t act, int64_t math) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  if (b.has_value()) check_operand(*b, "bias");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(1) == x.size(1) && w.size(2) == w.size(3), "conv2d: weight ", w.sizes(),
-              " does not match input ", x.sizes());
+// ---------------------------------------------------------------- conv2d / conv_transpose2d
+// One launcher per op family (forward, input gradient, weight gradient), each for both kinds of conv (TR: the
+// transposed one, weight [Cin][Cout][k][k]; else [Cout][Cin][k][k]); the registered ops below are bindings of
+// them.  A family's *_out function allocates its outputs, for the launcher and for the op's shape (Meta) kernel.
+// What a binding chooses: a bf16 copy of an operand (include/imgcomp.h *_xb; none: nullptr), a caller-owned
+// workspace (the forwards; none: nullptr), and its own name for the messages.
+template <bool TR>
+Tensor conv_fwd_out(const Tensor& x, const Tensor& w, int64_t stride, int64_t pad, int64_t opad) {
   const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) + 2 * pad - k) / stride + 1, wo = (x.size(3) + 2 * pad - k) / stride + 1;
-  Tensor y = new_act(x, x.size(0), w.size(0), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_conv2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)math);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_conv2d_fwd_ex(&ax, w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride, (int)pad, &ay, (int)act,
-                            (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "conv2d_fwd");
-  return y;
+  const int64_t ho = TR ? (x.size(2) - 1) * stride - 2 * pad + k + opad : (x.size(2) + 2 * pad - k) / stride + 1;
+  const int64_t wo = TR ? (x.size(3) - 1) * stride - 2 * pad + k + opad : (x.size(3) + 2 * pad - k) / stride + 1;
+  return new_act(x, x.size(0), w.size(TR ? 1 : 0), ho, wo);
 }
 
-// The forward with a caller-owned workspace that persists across calls (eval-mode weight caching,
-// functional._cached_fwd): grown here when too small (only on a packing call — with IC_MATH_WPACKED the
-// pack must already be in it, so a short workspace is an error).
+// dx has x's shape; its memory format is x's (like_x) or the one of its channel count (act_format)
+Tensor conv_dgrad_out(const Tensor& dy, const Tensor& x, bool like_x) {
+  return at::empty(x.sizes(), dy.options().memory_format(like_x ? x.suggest_memory_format() : act_format(x.size(1))));
+}
+
+// (dw, db); db is empty when bias is false
+template <bool TR>
+std::tuple<Tensor, Tensor> conv_wgrad_out(const Tensor& w, bool bias) {
+  Tensor dw = at::empty_like(w, at::MemoryFormat::Contiguous);
+  return {dw, at::empty({bias ? w.size(TR ? 1 : 0) : 0}, w.options())};
+}
+
+// x is the conv's input; dy (the gradients) its output gradient
+template <bool TR>
+void check_weight(const Tensor& w, const Tensor& x, const Tensor* dy = nullptr) {
+  TORCH_CHECK(w.dim() == 4 && w.size(TR ? 0 : 1) == x.size(1) && w.size(2) == w.size(3),
+              TR ? "conv_transpose2d: weight " : "conv2d: weight ", w.sizes(), " does not match input ", x.sizes());
+  TORCH_CHECK(!dy || (dy->dim() == 4 && dy->size(1) == w.size(TR ? 1 : 0)),
+              TR ? "conv_transpose2d: weight " : "conv2d: weight ", w.sizes(), " does not match the output gradient");
+}
+
+void check_copy(const Tensor& b, const Tensor& like, const char* what) {
+  TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kBFloat16 && b.sizes() == like.sizes() &&
+                  b.strides() == like.strides(),
+              "imgcomp: ", what, " must be a bf16 tensor with the shape and strides of its fp32 tensor");
+}
+
+// A caller-owned workspace that persists across calls (eval-mode weight caching, functional._cached_conv) is
+// grown here when too small (only on a packing call — with IC_MATH_WPACKED the pack must already be in it, so a
+// short workspace is an error).
 void ensure_ws(Tensor& ws, size_t nb, int64_t math, const char* what) {
   if ((size_t)ws.numel() >= nb) return;
   TORCH_CHECK(!(math & IC_MATH_WPACKED), "imgcomp: ", what, ": IC_MATH_WPACKED with a workspace of ", ws.numel(),
               " bytes, the op needs ", nb);
   ws.resize_({(int64_t)nb});
 }
+
+template <bool TR>
+Tensor conv_fwd(const char* what, const Tensor& x, const Tensor* xb, const Tensor& w, const c10::optional<Tensor>& b,
+                int64_t stride, int64_t pad, int64_t opad, int64_t act, int64_t math, Tensor* own_ws) {
+  check_operand(x, "x");
+  check_operand(w, "weight");
+  if (b.has_value()) check_operand(*b, "bias");
+  if (xb) check_copy(*xb, x, "xb");
+  TORCH_CHECK(!own_ws || (own_ws->device() == x.device() && own_ws->scalar_type() == at::kByte && own_ws->dim() == 1 &&
+                          own_ws->is_contiguous()),
+              what, ": the workspace must be a contiguous uint8 vector on the input's device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  check_weight<TR>(w, x);
+  Tensor y = conv_fwd_out<TR>(x, w, stride, pad, opad);
+  const ic_act ax = act_of(x), ay = act_of(y);
+  const int k = (int)w.size(2);
+  // the query: with the copy's tiles; of a packing call, whether or not this call packs
+  const int qmath = own_ws ? (int)(math & ~IC_MATH_WPACKED) : xb ? (int)math | IC_MATH_XB : (int)math;
+  const size_t nb = (TR ? ic_conv_transpose2d_fwd_ws_ex : ic_conv2d_fwd_ws_ex)(&ax, k, (int)stride, (int)pad, &ay, qmath);
+  Tensor tmp;
+  if (own_ws) ensure_ws(*own_ws, nb, math, what);
+  else tmp = workspace(x, nb);
+  void* ws = own_ws ? own_ws->data_ptr() : tmp.data_ptr();
+  const size_t ws_bytes = own_ws ? (size_t)own_ws->numel() : nb;
+  check_rc(xb ? (TR ? ic_conv_transpose2d_fwd_xb : ic_conv2d_fwd_xb)(&ax, xb->data_ptr(), w.data_ptr<float>(), opt_ptr(b),
+                                                                    k, (int)stride, (int)pad, &ay, (int)act, (int)math,
+                                                                    ws, ws_bytes, stream_of(x))
+              : (TR ? ic_conv_transpose2d_fwd_ex : ic_conv2d_fwd_ex)(&ax, w.data_ptr<float>(), opt_ptr(b), k, (int)stride,
+                                                                    (int)pad, &ay, (int)act, (int)math, ws, ws_bytes,
+                                                                    stream_of(x)),
+           what);
+  return y;
+}
+
+// x: the conv's input, read for its shape and memory format only
+template <bool TR>
+Tensor conv_dgrad(const char* what, const Tensor& dy, const Tensor* dyb, const Tensor& w, const Tensor& x, int64_t stride,
+                  int64_t pad, int64_t math, bool like_x) {
+  check_operand(dy, "dy");
+  check_operand(w, "weight");
+  if (dyb) check_copy(*dyb, dy, "dyb");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  check_weight<TR>(w, x, &dy);
+  Tensor dx = conv_dgrad_out(dy, x, like_x);
+  const ic_act ag = act_of(dy), adx = act_of(dx);
+  const int k = (int)w.size(2);
+  const size_t nb = (TR ? ic_conv_transpose2d_dgrad_ws_ex : ic_conv2d_dgrad_ws_ex)(&ag, k, (int)stride, (int)pad, &adx,
+                                                                                   dyb ? (int)math | IC_MATH_XB : (int)math);
+  Tensor ws = workspace(dy, nb);
+  check_rc(dyb ? (TR ? ic_conv_transpose2d_dgrad_xb : ic_conv2d_dgrad_xb)(&ag, dyb->data_ptr(), w.data_ptr<float>(), k,
+                                                                         (int)stride, (int)pad, &adx, (int)math,
+                                                                         ws.data_ptr(), nb, stream_of(dy))
+               : (TR ? ic_conv_transpose2d_dgrad_ex : ic_conv2d_dgrad_ex)(&ag, w.data_ptr<float>(), k, (int)stride, (int)pad,
+                                                                         &adx, (int)math, ws.data_ptr(), nb, stream_of(dy)),
+           what);
+  return dx;
+}
+
+// xb and dyb: both or neither.  w is read for its shape only.
+template <bool TR>
+std::tuple<Tensor, Tensor> conv_wgrad(const char* what, const Tensor& x, const Tensor* xb, const Tensor& dy,
+                                      const Tensor* dyb, const Tensor& w, int64_t stride, int64_t pad, bool bias,
+                                      int64_t math) {
+  check_operand(x, "x");
+  check_operand(dy, "dy");
+  check_operand(w, "weight");
+  if (xb) check_copy(*xb, x, "xb");
+  if (dyb) check_copy(*dyb, dy, "dyb");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
+  check_weight<TR>(w, x, &dy);
+  std::tuple<Tensor, Tensor> out = conv_wgrad_out<TR>(w, bias);
+  float* dw = std::get<0>(out).data_ptr<float>();
+  float* db = bias ? std::get<1>(out).data_ptr<float>() : nullptr;
+  const ic_act ax = act_of(x), ag = act_of(dy);
+  const int k = (int)w.size(2);
+  const size_t nb = (TR ? ic_conv_transpose2d_wgrad_ws_ex : ic_conv2d_wgrad_ws_ex)(&ax, &ag, k, (int)stride, (int)pad,
+                                                                                   (int)math);
+  Tensor ws = workspace(dy, nb);
+  check_rc(xb ? (TR ? ic_conv_transpose2d_wgrad_xb : ic_conv2d_wgrad_xb)(&ax, xb->data_ptr(), &ag, dyb->data_ptr(), k,
+                                                                        (int)stride, (int)pad, dw, db, (int)math,
+                                                                        ws.data_ptr(), nb, stream_of(dy))
+              : (TR ? ic_conv_transpose2d_wgrad_ex : ic_conv2d_wgrad_ex)(&ax, &ag, k, (int)stride, (int)pad, dw, db,
+                                                                        (int)math, ws.data_ptr(), nb, stream_of(dy)),
+           what);
+  return out;
+}
+
+// The registered ops.  dx's memory format (the last argument of conv_dgrad): conv2d_dgrad gives dx x's own, every
+// other input gradient the format of x's channel count.  The two differ only for an x of >= 32 channels that is
+// not channels-last or an x of < 32 channels that is; functional passes neither (functional._cl).
+Tensor conv2d_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride, int64_t pad,
+                  int64_t act, int64_t math) {
+  return conv_fwd<false>("conv2d_fwd", x, nullptr, w, b, stride, pad, 0, act, math, nullptr);
+}
 Tensor conv2d_fwd_ws(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride, int64_t pad,
                      int64_t act, int64_t math, Tensor& ws) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  if (b.has_value()) check_operand(*b, "bias");
-  TORCH_CHECK(ws.device() == x.device() && ws.scalar_type() == at::kByte && ws.dim() == 1 && ws.is_contiguous(),
-              "conv2d_fwd_ws: the workspace must be a contiguous uint8 vector on the input's device");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(1) == x.size(1) && w.size(2) == w.size(3), "conv2d: weight ", w.sizes(),
-              " does not match input ", x.sizes());
-  const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) + 2 * pad - k) / stride + 1, wo = (x.size(3) + 2 * pad - k) / stride + 1;
-  Tensor y = new_act(x, x.size(0), w.size(0), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_conv2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)(math & ~IC_MATH_WPACKED));
-  ensure_ws(ws, nb, math, "conv2d_fwd_ws");
-  check_rc(ic_conv2d_fwd_ex(&ax, w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride, (int)pad, &ay, (int)act,
-                            (int)math, ws.data_ptr(), (size_t)ws.numel(), stream_of(x)),
-           "conv2d_fwd_ws");
-  return y;
-}
-Tensor conv_transpose2d_fwd_ws(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
-                               int64_t pad, int64_t output_padding, int64_t act, int64_t math, Tensor& ws) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  if (b.has_value()) check_operand(*b, "bias");
-  TORCH_CHECK(ws.device() == x.device() && ws.scalar_type() == at::kByte && ws.dim() == 1 && ws.is_contiguous(),
-              "conv_transpose2d_fwd_ws: the workspace must be a contiguous uint8 vector on the input's device");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == x.size(1) && w.size(2) == w.size(3), "conv_transpose2d: weight ",
-              w.sizes(), " does not match input ", x.sizes());
-  const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) - 1) * stride - 2 * pad + k + output_padding;
-  const int64_t wo = (x.size(3) - 1) * stride - 2 * pad + k + output_padding;
-  Tensor y = new_act(x, x.size(0), w.size(1), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb =
-      ic_conv_transpose2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)(math & ~IC_MATH_WPACKED));
-  ensure_ws(ws, nb, math, "conv_transpose2d_fwd_ws");
-  check_rc(ic_conv_transpose2d_fwd_ex(&ax, w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride, (int)pad, &ay,
-                                      (int)act, (int)math, ws.data_ptr(), (size_t)ws.numel(), stream_of(x)),
-           "conv_transpose2d_fwd_ws");
-  return y;
-}
-
-// dx has the shape and memory format of x
-Tensor conv2d_dgrad(const Tensor& dy, const Tensor& w, const Tensor& x, int64_t stride, int64_t pad, int64_t math) {
-  check_operand(dy, "dy");
-  check_operand(w, "weight");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dx = at::empty(x.sizes(), dy.options().memory_format(x.suggest_memory_format()));
-  const ic_act ag = act_of(dy), adx = act_of(dx);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv2d_dgrad_ws_ex(&ag, k, (int)stride, (int)pad, &adx, (int)math);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv2d_dgrad_ex(&ag, w.data_ptr<float>(), k, (int)stride, (int)pad, &adx, (int)math, ws.data_ptr(), nb,
-                              stream_of(dy)),
-           "conv2d_dgrad");
-  return dx;
-}
-
-// (dw, db); db is empty when bias is false
-std::tuple<Tensor, Tensor> conv2d_wgrad(const Tensor& x, const Tensor& dy, const Tensor& w, int64_t stride, int64_t pad,
-                                        bool bias, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dw = at::empty_like(w, at::MemoryFormat::Contiguous);
-  Tensor db = at::empty({bias ? w.size(0) : 0}, w.options());
-  const ic_act ax = act_of(x), ag = act_of(dy);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv2d_wgrad_ws_ex(&ax, &ag, k, (int)stride, (int)pad, (int)math);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv2d_wgrad_ex(&ax, &ag, k, (int)stride, (int)pad, dw.data_ptr<float>(),
-                              bias ? db.data_ptr<float>() : nullptr, (int)math, ws.data_ptr(), nb, stream_of(dy)),
-           "conv2d_wgrad");
-  return {dw, db};
-}
-
-// ---------------------------------------------------------------- conv_transpose2d
-Tensor conv_transpose2d_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
-                            int64_t pad, int64_t output_padding, int64_t act, int64_t math) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  if (b.has_value()) check_operand(*b, "bias");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == x.size(1) && w.size(2) == w.size(3), "conv_transpose2d: weight ",
-              w.sizes(), " does not match input ", x.sizes());
-  const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) - 1) * stride - 2 * pad + k + output_padding;
-  const int64_t wo = (x.size(3) - 1) * stride - 2 * pad + k + output_padding;
-  Tensor y = new_act(x, x.size(0), w.size(1), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_conv_transpose2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)math);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_conv_transpose2d_fwd_ex(&ax, w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride, (int)pad, &ay,
-                                      (int)act, (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "conv_transpose2d_fwd");
-  return y;
-}
-
-Tensor conv_transpose2d_dgrad(const Tensor& dy, const Tensor& w, const Tensor& x, int64_t stride, int64_t pad,
-                              int64_t math) {
-  check_operand(dy, "dy");
-  check_operand(w, "weight");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dx = new_act(dy, x.size(0), x.size(1), x.size(2), x.size(3));
-  const ic_act ag = act_of(dy), adx = act_of(dx);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv_transpose2d_dgrad_ws_ex(&ag, k, (int)stride, (int)pad, &adx, (int)math);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv_transpose2d_dgrad_ex(&ag, w.data_ptr<float>(), k, (int)stride, (int)pad, &adx, (int)math,
-                                        ws.data_ptr(), nb, stream_of(dy)),
-           "conv_transpose2d_dgrad");
-  return dx;
-}
-
-std::tuple<Tensor, Tensor> conv_transpose2d_wgrad(const Tensor& x, const Tensor& dy, const Tensor& w, int64_t stride,
-                                                  int64_t pad, bool bias, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dw = at::empty_like(w, at::MemoryFormat::Contiguous);
-  Tensor db = at::empty({bias ? w.size(1) : 0}, w.options());
-  const ic_act ax = act_of(x), ag = act_of(dy);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv_transpose2d_wgrad_ws_ex(&ax, &ag, k, (int)stride, (int)pad, (int)math);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv_transpose2d_wgrad_ex(&ax, &ag, k, (int)stride, (int)pad, dw.data_ptr<float>(),
-                                        bias ? db.data_ptr<float>() : nullptr, (int)math, ws.data_ptr(), nb,
-                                        stream_of(dy)),
-           "conv_transpose2d_wgrad");
-  return {dw, db};
-}
-
-// ---------------------------------------------------------------- GDN
-// gamma [C][C] (or [C][C][1][1]), beta [C], already re-parameterised (NonNegativeParam)
-std::tuple<Tensor, Tensor> gdn_fwd(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
-                                   int64_t math) {
-  check_operand(x, "x");
-  check_operand(gamma, "gamma");
-  check_operand(beta, "beta");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(gamma.numel() == x.size(1) * x.size(1) && beta.numel() == x.size(1), "gdn: parameters do not match ",
-              x.sizes());
-  Tensor y = at::empty_like(x);
-  Tensor norm = at::empty_like(x);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_gdn_fwd_ws_ex(&ax, (int)math);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_fwd_ex(&ax, gamma.data_ptr<float>(), beta.data_ptr<float>(), inverse ? 1 : 0, &ay,
-                         norm.data_ptr<float>(), (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "gdn_fwd");
-  return {y, norm};
-}
-
-// dy must have x's strides (the caller matches them)
-std::tuple<Tensor, Tensor, Tensor> gdn_bwd(const Tensor& x, const Tensor& norm, const Tensor& dy, const Tensor& gamma,
-                                           bool inverse, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "gdn_bwd: dy must have x's shape and strides");
-  Tensor dx = at::empty_like(x);
-  Tensor dg = at::empty_like(gamma, at::MemoryFormat::Contiguous);
-  Tensor dbeta = at::empty({x.size(1)}, gamma.options());
-  const ic_act ax = act_of(x), adx = act_of(dx);
-  const size_t nb = ic_gdn_bwd_ws(&ax);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_bwd_ex(&ax, norm.data_ptr<float>(), dy.data_ptr<float>(), gamma.data_ptr<float>(), inverse ? 1 : 0,
-                         &adx, dg.data_ptr<float>(), dbeta.data_ptr<float>(), (int)math, ws.data_ptr(), nb,
-                         stream_of(x)),
-           "gdn_bwd");
-  return {dx, dg, dbeta};
-}
-
-// gdn_bwd plus the column sums of dx over all pixels (the producing conv's bias gradient)
-std::tuple<Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum(const Tensor& x, const Tensor& norm, const Tensor& dy,
-                                                       const Tensor& gamma, bool inverse, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "gdn_bwd_sum: dy must have x's shape and strides");
-  Tensor dx = at::empty_like(x);
-  Tensor dg = at::empty_like(gamma, at::MemoryFormat::Contiguous);
-  Tensor dbeta = at::empty({x.size(1)}, gamma.options());
-  Tensor dxsum = at::empty({x.size(1)}, gamma.options());
-  const ic_act ax = act_of(x), adx = act_of(dx);
-  const size_t nb = ic_gdn_bwd_ws(&ax);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_bwd_sum_ex(&ax, norm.data_ptr<float>(), dy.data_ptr<float>(), gamma.data_ptr<float>(),
-                             inverse ? 1 : 0, &adx, dg.data_ptr<float>(), dbeta.data_ptr<float>(),
-                             dxsum.data_ptr<float>(), (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "gdn_bwd_sum");
-  return {dx, dg, dbeta, dxsum};
-}
-
-
-// ---------------------------------------------------------------- bf16 activation copies (C3)
-// The GDN output / input gradient also as a bf16 tensor of the same shape and strides (compact NHWC),
-// and the conv forward / transposed-conv input gradient that reads such a copy (include/imgcomp.h
-// ic_gdn_fwd_xb, ic_gdn_bwd_sum_xb, ic_conv2d_fwd_xb, ic_conv_transpose2d_dgrad_xb).
-void check_copy(const Tensor& b, const Tensor& like, const char* what) {
-  TORCH_CHECK(b.is_cuda() && b.scalar_type() == at::kBFloat16 && b.sizes() == like.sizes() &&
-                  b.strides() == like.strides(),
-              "imgcomp: ", what, " must be a bf16 tensor with the shape and strides of its fp32 tensor");
-}
-std::tuple<Tensor, Tensor, Tensor> gdn_fwd_xb(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
-                                              int64_t math) {
-  check_operand(x, "x");
-  check_operand(gamma, "gamma");
-  check_operand(beta, "beta");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(gamma.numel() == x.size(1) * x.size(1) && beta.numel() == x.size(1), "gdn: parameters do not match ",
-              x.sizes());
-  Tensor y = at::empty_like(x);
-  Tensor norm = at::empty_like(x);
-  Tensor yb = at::empty_like(x, x.options().dtype(at::kBFloat16));
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_gdn_fwd_ws_ex(&ax, (int)math);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_fwd_xb(&ax, gamma.data_ptr<float>(), beta.data_ptr<float>(), inverse ? 1 : 0, &ay,
-                         norm.data_ptr<float>(), yb.data_ptr(), (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "gdn_fwd_xb");
-  return {y, norm, yb};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_xb(const Tensor& x, const Tensor& norm, const Tensor& dy,
-                                                                  const Tensor& gamma, bool inverse, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "gdn_bwd_sum_xb: dy must have x's shape and strides");
-  Tensor dx = at::empty_like(x);
-  Tensor dg = at::empty_like(gamma, at::MemoryFormat::Contiguous);
-  Tensor dbeta = at::empty({x.size(1)}, gamma.options());
-  Tensor dxsum = at::empty({x.size(1)}, gamma.options());
-  Tensor dxb = at::empty_like(x, x.options().dtype(at::kBFloat16));
-  const ic_act ax = act_of(x), adx = act_of(dx);
-  const size_t nb = ic_gdn_bwd_ws(&ax);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_bwd_sum_xb(&ax, norm.data_ptr<float>(), dy.data_ptr<float>(), gamma.data_ptr<float>(),
-                             inverse ? 1 : 0, &adx, dg.data_ptr<float>(), dbeta.data_ptr<float>(),
-                             dxsum.data_ptr<float>(), dxb.data_ptr(), (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "gdn_bwd_sum_xb");
-  return {dx, dg, dbeta, dxsum, dxb};
-}
-// norm recomputed (C3, round 6; include/imgcomp.h ic_gdn_fwd_rn / ic_gdn_bwd_sum_rn): the forward leaves norm
-// out, the backward forms it again from x, gamma and beta.  xb: also the bf16 copy of y / dx (else an empty
-// bf16 tensor is returned in its place).
-std::tuple<Tensor, Tensor> gdn_fwd_rn(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
-                                      int64_t math, bool xb) {
-  check_operand(x, "x");
-  check_operand(gamma, "gamma");
-  check_operand(beta, "beta");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(gamma.numel() == x.size(1) * x.size(1) && beta.numel() == x.size(1), "gdn: parameters do not match ",
-              x.sizes());
-  Tensor y = at::empty_like(x);
-  Tensor yb = xb ? at::empty_like(x, x.options().dtype(at::kBFloat16)) : at::empty({0}, x.options().dtype(at::kBFloat16));
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_gdn_fwd_ws_ex(&ax, (int)math);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_fwd_rn(&ax, gamma.data_ptr<float>(), beta.data_ptr<float>(), inverse ? 1 : 0, &ay,
-                         xb ? yb.data_ptr() : nullptr, (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "gdn_fwd_rn");
-  return {y, yb};
-}
-std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_rn(const Tensor& x, const Tensor& beta, const Tensor& dy,
-                                                                  const Tensor& gamma, bool inverse, int64_t math,
-                                                                  bool xb) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  check_operand(beta, "beta");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), "gdn_bwd_sum_rn: dy must have x's shape and strides");
-  TORCH_CHECK(beta.numel() == x.size(1), "gdn_bwd_sum_rn: beta does not match ", x.sizes());
-  Tensor dx = at::empty_like(x);
-  Tensor dg = at::empty_like(gamma, at::MemoryFormat::Contiguous);
-  Tensor dbeta = at::empty({x.size(1)}, gamma.options());
-  Tensor dxsum = at::empty({x.size(1)}, gamma.options());
-  Tensor dxb = xb ? at::empty_like(x, x.options().dtype(at::kBFloat16)) : at::empty({0}, x.options().dtype(at::kBFloat16));
-  const ic_act ax = act_of(x), adx = act_of(dx);
-  const size_t nb = ic_gdn_bwd_ws(&ax);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_gdn_bwd_sum_rn(&ax, beta.data_ptr<float>(), dy.data_ptr<float>(), gamma.data_ptr<float>(),
-                             inverse ? 1 : 0, &adx, dg.data_ptr<float>(), dbeta.data_ptr<float>(),
-                             dxsum.data_ptr<float>(), xb ? dxb.data_ptr() : nullptr, (int)math, ws.data_ptr(), nb,
-                             stream_of(x)),
-           "gdn_bwd_sum_rn");
-  return {dx, dg, dbeta, dxsum, dxb};
+  return conv_fwd<false>("conv2d_fwd_ws", x, nullptr, w, b, stride, pad, 0, act, math, &ws);
 }
 Tensor conv2d_fwd_xb(const Tensor& x, const Tensor& xb, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
                      int64_t pad, int64_t act, int64_t math) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  check_copy(xb, x, "xb");
-  if (b.has_value()) check_operand(*b, "bias");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(1) == x.size(1) && w.size(2) == w.size(3), "conv2d: weight ", w.sizes(),
-              " does not match input ", x.sizes());
-  const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) + 2 * pad - k) / stride + 1, wo = (x.size(3) + 2 * pad - k) / stride + 1;
-  Tensor y = new_act(x, x.size(0), w.size(0), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_conv2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)math | IC_MATH_XB);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_conv2d_fwd_xb(&ax, xb.data_ptr(), w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride, (int)pad, &ay,
-                            (int)act, (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "conv2d_fwd_xb");
-  return y;
+  return conv_fwd<false>("conv2d_fwd_xb", x, &xb, w, b, stride, pad, 0, act, math, nullptr);
 }
-Tensor conv_transpose2d_dgrad_xb(const Tensor& dy, const Tensor& dyb, const Tensor& w, const Tensor& x, int64_t stride,
-                                 int64_t pad, int64_t math) {
-  check_operand(dy, "dy");
-  check_operand(w, "weight");
-  check_copy(dyb, dy, "dyb");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dx = new_act(dy, x.size(0), x.size(1), x.size(2), x.size(3));
-  const ic_act ag = act_of(dy), adx = act_of(dx);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv_transpose2d_dgrad_ws_ex(&ag, k, (int)stride, (int)pad, &adx, (int)math | IC_MATH_XB);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv_transpose2d_dgrad_xb(&ag, dyb.data_ptr(), w.data_ptr<float>(), k, (int)stride, (int)pad, &adx,
-                                        (int)math, ws.data_ptr(), nb, stream_of(dy)),
-           "conv_transpose2d_dgrad_xb");
-  return dx;
+Tensor conv_transpose2d_fwd(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
+                            int64_t pad, int64_t opad, int64_t act, int64_t math) {
+  return conv_fwd<true>("conv_transpose2d_fwd", x, nullptr, w, b, stride, pad, opad, act, math, nullptr);
 }
-
-Tensor conv2d_dgrad_xb(const Tensor& dy, const Tensor& dyb, const Tensor& w, const Tensor& x, int64_t stride,
-                       int64_t pad, int64_t math) {
-  check_operand(dy, "dy");
-  check_operand(w, "weight");
-  check_copy(dyb, dy, "dyb");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dx = new_act(dy, x.size(0), x.size(1), x.size(2), x.size(3));
-  const ic_act ag = act_of(dy), adx = act_of(dx);
-  const int k = (int)w.size(2);
-  const size_t nb = ic_conv2d_dgrad_ws_ex(&ag, k, (int)stride, (int)pad, &adx, (int)math | IC_MATH_XB);
-  Tensor ws = workspace(dy, nb);
-  check_rc(ic_conv2d_dgrad_xb(&ag, dyb.data_ptr(), w.data_ptr<float>(), k, (int)stride, (int)pad, &adx, (int)math,
-                              ws.data_ptr(), nb, stream_of(dy)),
-           "conv2d_dgrad_xb");
-  return dx;
+Tensor conv_transpose2d_fwd_ws(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
+                               int64_t pad, int64_t opad, int64_t act, int64_t math, Tensor& ws) {
+  return conv_fwd<true>("conv_transpose2d_fwd_ws", x, nullptr, w, b, stride, pad, opad, act, math, &ws);
 }
 Tensor conv_transpose2d_fwd_xb(const Tensor& x, const Tensor& xb, const Tensor& w, const c10::optional<Tensor>& b,
                                int64_t stride, int64_t pad, int64_t opad, int64_t act, int64_t math) {
-  check_operand(x, "x");
-  check_operand(w, "weight");
-  check_copy(xb, x, "xb");
-  if (b.has_value()) check_operand(*b, "bias");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  TORCH_CHECK(w.dim() == 4 && w.size(0) == x.size(1) && w.size(2) == w.size(3), "conv_transpose2d: weight ", w.sizes(),
-              " does not match input ", x.sizes());
-  const int64_t k = w.size(2);
-  const int64_t ho = (x.size(2) - 1) * stride - 2 * pad + k + opad, wo = (x.size(3) - 1) * stride - 2 * pad + k + opad;
-  Tensor y = new_act(x, x.size(0), w.size(1), ho, wo);
-  const ic_act ax = act_of(x), ay = act_of(y);
-  const size_t nb = ic_conv_transpose2d_fwd_ws_ex(&ax, (int)k, (int)stride, (int)pad, &ay, (int)math | IC_MATH_XB);
-  Tensor ws = workspace(x, nb);
-  check_rc(ic_conv_transpose2d_fwd_xb(&ax, xb.data_ptr(), w.data_ptr<float>(), opt_ptr(b), (int)k, (int)stride,
-                                      (int)pad, &ay, (int)act, (int)math, ws.data_ptr(), nb, stream_of(x)),
-           "conv_transpose2d_fwd_xb");
-  return y;
+  return conv_fwd<true>("conv_transpose2d_fwd_xb", x, &xb, w, b, stride, pad, opad, act, math, nullptr);
 }
-
-template <bool TR>
-std::tuple<Tensor, Tensor> wgrad_xb(const Tensor& x, const Tensor& xb, const Tensor& dy, const Tensor& dyb,
-                                    const Tensor& w, int64_t stride, int64_t pad, bool bias, int64_t math) {
-  check_operand(x, "x");
-  check_operand(dy, "dy");
-  check_copy(xb, x, "xb");
-  check_copy(dyb, dy, "dyb");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(dy.device());
-  Tensor dw = at::empty_like(w, at::MemoryFormat::Contiguous);
-  Tensor db = at::empty({bias ? (TR ? w.size(1) : w.size(0)) : 0}, w.options());
-  const ic_act ax = act_of(x), ag = act_of(dy);
-  const int k = (int)w.size(2);
-  const size_t nb = TR ? ic_conv_transpose2d_wgrad_ws_ex(&ax, &ag, k, (int)stride, (int)pad, (int)math)
-                       : ic_conv2d_wgrad_ws_ex(&ax, &ag, k, (int)stride, (int)pad, (int)math);
-  Tensor ws = workspace(dy, nb);
-  float* dbp = bias ? db.data_ptr<float>() : nullptr;
-  const int rc = TR ? ic_conv_transpose2d_wgrad_xb(&ax, xb.data_ptr(), &ag, dyb.data_ptr(), k, (int)stride, (int)pad,
-                                                   dw.data_ptr<float>(), dbp, (int)math, ws.data_ptr(), nb,
-                                                   stream_of(dy))
-                    : ic_conv2d_wgrad_xb(&ax, xb.data_ptr(), &ag, dyb.data_ptr(), k, (int)stride, (int)pad,
-                                         dw.data_ptr<float>(), dbp, (int)math, ws.data_ptr(), nb, stream_of(dy));
-  check_rc(rc, TR ? "conv_transpose2d_wgrad_xb" : "conv2d_wgrad_xb");
-  return {dw, db};
+Tensor conv2d_dgrad(const Tensor& dy, const Tensor& w, const Tensor& x, int64_t stride, int64_t pad, int64_t math) {
+  return conv_dgrad<false>("conv2d_dgrad", dy, nullptr, w, x, stride, pad, math, true);
+}
+Tensor conv2d_dgrad_xb(const Tensor& dy, const Tensor& dyb, const Tensor& w, const Tensor& x, int64_t stride,
+                       int64_t pad, int64_t math) {
+  return conv_dgrad<false>("conv2d_dgrad_xb", dy, &dyb, w, x, stride, pad, math, false);
+}
+Tensor conv_transpose2d_dgrad(const Tensor& dy, const Tensor& w, const Tensor& x, int64_t stride, int64_t pad,
+                              int64_t math) {
+  return conv_dgrad<true>("conv_transpose2d_dgrad", dy, nullptr, w, x, stride, pad, math, false);
+}
+Tensor conv_transpose2d_dgrad_xb(const Tensor& dy, const Tensor& dyb, const Tensor& w, const Tensor& x, int64_t stride,
+                                 int64_t pad, int64_t math) {
+  return conv_dgrad<true>("conv_transpose2d_dgrad_xb", dy, &dyb, w, x, stride, pad, math, false);
+}
+std::tuple<Tensor, Tensor> conv2d_wgrad(const Tensor& x, const Tensor& dy, const Tensor& w, int64_t stride, int64_t pad,
+                                        bool bias, int64_t math) {
+  return conv_wgrad<false>("conv2d_wgrad", x, nullptr, dy, nullptr, w, stride, pad, bias, math);
 }
 std::tuple<Tensor, Tensor> conv2d_wgrad_xb(const Tensor& x, const Tensor& xb, const Tensor& dy, const Tensor& dyb,
                                            const Tensor& w, int64_t stride, int64_t pad, bool bias, int64_t math) {
-  return wgrad_xb<false>(x, xb, dy, dyb, w, stride, pad, bias, math);
+  return conv_wgrad<false>("conv2d_wgrad_xb", x, &xb, dy, &dyb, w, stride, pad, bias, math);
+}
+std::tuple<Tensor, Tensor> conv_transpose2d_wgrad(const Tensor& x, const Tensor& dy, const Tensor& w, int64_t stride,
+                                                  int64_t pad, bool bias, int64_t math) {
+  return conv_wgrad<true>("conv_transpose2d_wgrad", x, nullptr, dy, nullptr, w, stride, pad, bias, math);
 }
 std::tuple<Tensor, Tensor> conv_transpose2d_wgrad_xb(const Tensor& x, const Tensor& xb, const Tensor& dy,
                                                      const Tensor& dyb, const Tensor& w, int64_t stride, int64_t pad,
                                                      bool bias, int64_t math) {
-  return wgrad_xb<true>(x, xb, dy, dyb, w, stride, pad, bias, math);
+  return conv_wgrad<true>("conv_transpose2d_wgrad_xb", x, &xb, dy, &dyb, w, stride, pad, bias, math);
+}
+
+// ---------------------------------------------------------------- GDN
+// gamma [C][C] (or [C][C][1][1]), beta [C], already re-parameterised (NonNegativeParam).  One launcher for the
+// forwards and one for the backwards; what varies (include/imgcomp.h ic_gdn_*):
+//   norm: stored by the forward and read by the backward, or left out and formed again by the backward from x,
+//         gamma and beta (_rn: C3, round 6), which then takes beta where the others take norm;
+//   the bf16 copy of y / dx beside the fp32 tensor, of the same shape and strides (_xb, _rn: C3), for the conv that
+//         reads it: no such output, an empty bf16 tensor in its place, or the copy;
+//   dxsum: the column sums of dx over all pixels (the producing conv's bias gradient).
+enum class Copy { None, Empty, Full };
+
+Tensor copy_out(const Tensor& x, Copy copy) {
+  if (copy == Copy::None) return Tensor();
+  return copy == Copy::Full ? at::empty_like(x, x.options().dtype(at::kBFloat16))
+                            : at::empty({0}, x.options().dtype(at::kBFloat16));
+}
+
+struct GdnFwd {
+  Tensor y, norm, yb;
+};
+GdnFwd gdn_fwd_out(const Tensor& x, bool norm, Copy copy) {
+  return {at::empty_like(x), norm ? at::empty_like(x) : Tensor(), copy_out(x, copy)};
+}
+
+struct GdnBwd {
+  Tensor dx, dg, dbeta, dxsum, dxb;
+};
+GdnBwd gdn_bwd_out(const Tensor& x, const Tensor& gamma, bool sum, Copy copy) {
+  return {at::empty_like(x), at::empty_like(gamma, at::MemoryFormat::Contiguous), at::empty({x.size(1)}, gamma.options()),
+          sum ? at::empty({x.size(1)}, gamma.options()) : Tensor(), copy_out(x, copy)};
+}
+
+GdnFwd gdn_forward(const char* what, const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
+                   int64_t math, bool norm, Copy copy) {
+  check_operand(x, "x");
+  check_operand(gamma, "gamma");
+  check_operand(beta, "beta");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  TORCH_CHECK(gamma.numel() == x.size(1) * x.size(1) && beta.numel() == x.size(1), "gdn: parameters do not match ",
+              x.sizes());
+  GdnFwd o = gdn_fwd_out(x, norm, copy);
+  const ic_act ax = act_of(x), ay = act_of(o.y);
+  const size_t nb = ic_gdn_fwd_ws_ex(&ax, (int)math);
+  Tensor ws = workspace(x, nb);
+  const float *g = gamma.data_ptr<float>(), *b = beta.data_ptr<float>();
+  void* yb = copy == Copy::Full ? o.yb.data_ptr() : nullptr;
+  const int inv = inverse ? 1 : 0;
+  check_rc(!norm ? ic_gdn_fwd_rn(&ax, g, b, inv, &ay, yb, (int)math, ws.data_ptr(), nb, stream_of(x))
+           : copy == Copy::Full
+               ? ic_gdn_fwd_xb(&ax, g, b, inv, &ay, o.norm.data_ptr<float>(), yb, (int)math, ws.data_ptr(), nb, stream_of(x))
+               : ic_gdn_fwd_ex(&ax, g, b, inv, &ay, o.norm.data_ptr<float>(), (int)math, ws.data_ptr(), nb, stream_of(x)),
+           what);
+  return o;
+}
+
+// nob: norm, or beta when the backward forms norm again (rn).  dy must have x's strides (the caller matches them).
+GdnBwd gdn_backward(const char* what, const Tensor& x, const Tensor& nob, bool rn, const Tensor& dy, const Tensor& gamma,
+                    bool inverse, int64_t math, bool sum, Copy copy) {
+  check_operand(x, "x");
+  check_operand(dy, "dy");
+  check_operand(nob, rn ? "beta" : "norm");
+  check_operand(gamma, "gamma");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.strides() == x.strides(), what, ": dy must have x's shape and strides");
+  TORCH_CHECK(!rn || nob.numel() == x.size(1), what, ": beta does not match ", x.sizes());
+  TORCH_CHECK(rn || (nob.sizes() == x.sizes() && nob.strides() == x.strides()), what,
+              ": norm must have x's shape and strides");
+  TORCH_CHECK(gamma.numel() == x.size(1) * x.size(1), "gdn: parameters do not match ", x.sizes());
+  GdnBwd o = gdn_bwd_out(x, gamma, sum, copy);
+  const ic_act ax = act_of(x), adx = act_of(o.dx);
+  const size_t wb = ic_gdn_bwd_ws(&ax);
+  Tensor ws = workspace(x, wb);
+  const float *np = nob.data_ptr<float>(), *gy = dy.data_ptr<float>(), *g = gamma.data_ptr<float>();
+  float *dg = o.dg.data_ptr<float>(), *dbeta = o.dbeta.data_ptr<float>();
+  float* dxsum = sum ? o.dxsum.data_ptr<float>() : nullptr;
+  void* dxb = copy == Copy::Full ? o.dxb.data_ptr() : nullptr;
+  const int inv = inverse ? 1 : 0;
+  check_rc(!sum ? ic_gdn_bwd_ex(&ax, np, gy, g, inv, &adx, dg, dbeta, (int)math, ws.data_ptr(), wb, stream_of(x))
+           : rn ? ic_gdn_bwd_sum_rn(&ax, np, gy, g, inv, &adx, dg, dbeta, dxsum, dxb, (int)math, ws.data_ptr(), wb,
+                                     stream_of(x))
+           : copy == Copy::Full
+               ? ic_gdn_bwd_sum_xb(&ax, np, gy, g, inv, &adx, dg, dbeta, dxsum, dxb, (int)math, ws.data_ptr(), wb,
+                                   stream_of(x))
+               : ic_gdn_bwd_sum_ex(&ax, np, gy, g, inv, &adx, dg, dbeta, dxsum, (int)math, ws.data_ptr(), wb,
+                                   stream_of(x)),
+           what);
+  return o;
+}
+
+std::tuple<Tensor, Tensor> gdn_fwd(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
+                                   int64_t math) {
+  GdnFwd o = gdn_forward("gdn_fwd", x, gamma, beta, inverse, math, true, Copy::None);
+  return {o.y, o.norm};
+}
+std::tuple<Tensor, Tensor, Tensor> gdn_fwd_xb(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
+                                              int64_t math) {
+  GdnFwd o = gdn_forward("gdn_fwd_xb", x, gamma, beta, inverse, math, true, Copy::Full);
+  return {o.y, o.norm, o.yb};
+}
+std::tuple<Tensor, Tensor> gdn_fwd_rn(const Tensor& x, const Tensor& gamma, const Tensor& beta, bool inverse,
+                                      int64_t math, bool xb) {
+  GdnFwd o = gdn_forward("gdn_fwd_rn", x, gamma, beta, inverse, math, false, xb ? Copy::Full : Copy::Empty);
+  return {o.y, o.yb};
+}
+std::tuple<Tensor, Tensor, Tensor> gdn_bwd(const Tensor& x, const Tensor& norm, const Tensor& dy, const Tensor& gamma,
+                                           bool inverse, int64_t math) {
+  GdnBwd o = gdn_backward("gdn_bwd", x, norm, false, dy, gamma, inverse, math, false, Copy::None);
+  return {o.dx, o.dg, o.dbeta};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum(const Tensor& x, const Tensor& norm, const Tensor& dy,
+                                                       const Tensor& gamma, bool inverse, int64_t math) {
+  GdnBwd o = gdn_backward("gdn_bwd_sum", x, norm, false, dy, gamma, inverse, math, true, Copy::None);
+  return {o.dx, o.dg, o.dbeta, o.dxsum};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_xb(const Tensor& x, const Tensor& norm, const Tensor& dy,
+                                                                  const Tensor& gamma, bool inverse, int64_t math) {
+  GdnBwd o = gdn_backward("gdn_bwd_sum_xb", x, norm, false, dy, gamma, inverse, math, true, Copy::Full);
+  return {o.dx, o.dg, o.dbeta, o.dxsum, o.dxb};
+}
+std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_rn(const Tensor& x, const Tensor& beta, const Tensor& dy,
+                                                                  const Tensor& gamma, bool inverse, int64_t math,
+                                                                  bool xb) {
+  GdnBwd o = gdn_backward("gdn_bwd_sum_rn", x, beta, true, dy, gamma, inverse, math, true, xb ? Copy::Full : Copy::Empty);
+  return {o.dx, o.dg, o.dbeta, o.dxsum, o.dxb};
 }
 
 // ---------------------------------------------------------------- elementwise, losses, entropy models
@@ -945,100 +838,79 @@ std::tuple<Tensor, Tensor> msssim_bwd(const Tensor& g_, const Tensor& state, at:
 }
 
 // ---------------------------------------------------------------- shape (Meta) kernels
+// conv / GDN: the *_out function of the op's family (above), with the op's own choices
 Tensor conv2d_fwd_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t stride, int64_t pad,
                        int64_t, int64_t) {
-  const int64_t k = w.size(2);
-  return at::empty({x.size(0), w.size(0), (x.size(2) + 2 * pad - k) / stride + 1, (x.size(3) + 2 * pad - k) / stride + 1},
-                   x.options().memory_format(act_format(w.size(0))));
+  return conv_fwd_out<false>(x, w, stride, pad, 0);
 }
-Tensor conv2d_fwd_ws_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b, int64_t stride,
-                          int64_t pad, int64_t act, int64_t math, Tensor&) {
-  return conv2d_fwd_meta(x, w, b, stride, pad, act, math);
+Tensor conv2d_fwd_ws_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t stride, int64_t pad,
+                          int64_t, int64_t, Tensor&) {
+  return conv_fwd_out<false>(x, w, stride, pad, 0);
 }
-Tensor conv2d_dgrad_meta(const Tensor& dy, const Tensor&, const Tensor& x, int64_t, int64_t, int64_t) {
-  return at::empty(x.sizes(), dy.options().memory_format(x.suggest_memory_format()));
-}
-std::tuple<Tensor, Tensor> conv2d_wgrad_meta(const Tensor&, const Tensor&, const Tensor& w, int64_t, int64_t, bool bias,
-                                             int64_t) {
-  return {at::empty_like(w, at::MemoryFormat::Contiguous), at::empty({bias ? w.size(0) : 0}, w.options())};
+Tensor conv2d_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor& w, const c10::optional<Tensor>&, int64_t stride,
+                          int64_t pad, int64_t, int64_t) {
+  return conv_fwd_out<false>(x, w, stride, pad, 0);
 }
 Tensor conv_transpose2d_fwd_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t stride,
-                                 int64_t pad, int64_t op, int64_t, int64_t) {
-  const int64_t k = w.size(2);
-  return at::empty({x.size(0), w.size(1), (x.size(2) - 1) * stride - 2 * pad + k + op,
-                    (x.size(3) - 1) * stride - 2 * pad + k + op},
-                   x.options().memory_format(act_format(w.size(1))));
+                                 int64_t pad, int64_t opad, int64_t, int64_t) {
+  return conv_fwd_out<true>(x, w, stride, pad, opad);
 }
-Tensor conv_transpose2d_fwd_ws_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>& b,
-                                    int64_t stride, int64_t pad, int64_t op, int64_t act, int64_t math, Tensor&) {
-  return conv_transpose2d_fwd_meta(x, w, b, stride, pad, op, act, math);
+Tensor conv_transpose2d_fwd_ws_meta(const Tensor& x, const Tensor& w, const c10::optional<Tensor>&, int64_t stride,
+                                    int64_t pad, int64_t opad, int64_t, int64_t, Tensor&) {
+  return conv_fwd_out<true>(x, w, stride, pad, opad);
 }
-Tensor conv_transpose2d_dgrad_meta(const Tensor& dy, const Tensor&, const Tensor& x, int64_t, int64_t, int64_t) {
-  return at::empty(x.sizes(), dy.options().memory_format(act_format(x.size(1))));
+Tensor conv_transpose2d_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor& w, const c10::optional<Tensor>&,
+                                    int64_t stride, int64_t pad, int64_t opad, int64_t, int64_t) {
+  return conv_fwd_out<true>(x, w, stride, pad, opad);
 }
-std::tuple<Tensor, Tensor> conv_transpose2d_wgrad_meta(const Tensor&, const Tensor&, const Tensor& w, int64_t, int64_t,
-                                                       bool bias, int64_t) {
-  return {at::empty_like(w, at::MemoryFormat::Contiguous), at::empty({bias ? w.size(1) : 0}, w.options())};
+template <bool LIKE_X>  // conv2d_dgrad alone
+Tensor conv_dgrad_meta(const Tensor& dy, const Tensor&, const Tensor& x, int64_t, int64_t, int64_t) {
+  return conv_dgrad_out(dy, x, LIKE_X);
+}
+Tensor conv_dgrad_xb_meta(const Tensor& dy, const Tensor&, const Tensor&, const Tensor& x, int64_t, int64_t, int64_t) {
+  return conv_dgrad_out(dy, x, false);
+}
+template <bool TR>
+std::tuple<Tensor, Tensor> conv_wgrad_meta(const Tensor&, const Tensor&, const Tensor& w, int64_t, int64_t, bool bias,
+                                           int64_t) {
+  return conv_wgrad_out<TR>(w, bias);
+}
+template <bool TR>
+std::tuple<Tensor, Tensor> conv_wgrad_xb_meta(const Tensor&, const Tensor&, const Tensor&, const Tensor&, const Tensor& w,
+                                              int64_t, int64_t, bool bias, int64_t) {
+  return conv_wgrad_out<TR>(w, bias);
 }
 std::tuple<Tensor, Tensor> gdn_fwd_meta(const Tensor& x, const Tensor&, const Tensor&, bool, int64_t) {
-  return {at::empty_like(x), at::empty_like(x)};
+  GdnFwd o = gdn_fwd_out(x, true, Copy::None);
+  return {o.y, o.norm};
+}
+std::tuple<Tensor, Tensor, Tensor> gdn_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor&, bool, int64_t) {
+  GdnFwd o = gdn_fwd_out(x, true, Copy::Full);
+  return {o.y, o.norm, o.yb};
+}
+std::tuple<Tensor, Tensor> gdn_fwd_rn_meta(const Tensor& x, const Tensor&, const Tensor&, bool, int64_t, bool xb) {
+  GdnFwd o = gdn_fwd_out(x, false, xb ? Copy::Full : Copy::Empty);
+  return {o.y, o.yb};
 }
 std::tuple<Tensor, Tensor, Tensor> gdn_bwd_meta(const Tensor& x, const Tensor&, const Tensor&, const Tensor& gamma, bool,
                                                 int64_t) {
-  return {at::empty_like(x), at::empty_like(gamma, at::MemoryFormat::Contiguous), at::empty({x.size(1)}, gamma.options())};
+  GdnBwd o = gdn_bwd_out(x, gamma, false, Copy::None);
+  return {o.dx, o.dg, o.dbeta};
 }
-
 std::tuple<Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_meta(const Tensor& x, const Tensor&, const Tensor&,
                                                             const Tensor& gamma, bool, int64_t) {
-  return {at::empty_like(x), at::empty_like(gamma, at::MemoryFormat::Contiguous), at::empty({x.size(1)}, gamma.options()),
-          at::empty({x.size(1)}, gamma.options())};
-}
-
-
-std::tuple<Tensor, Tensor, Tensor> gdn_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor&, bool, int64_t) {
-  return {at::empty_like(x), at::empty_like(x), at::empty_like(x, x.options().dtype(at::kBFloat16))};
+  GdnBwd o = gdn_bwd_out(x, gamma, true, Copy::None);
+  return {o.dx, o.dg, o.dbeta, o.dxsum};
 }
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_xb_meta(const Tensor& x, const Tensor&, const Tensor&,
                                                                        const Tensor& gamma, bool, int64_t) {
-  return {at::empty_like(x), at::empty_like(gamma, at::MemoryFormat::Contiguous), at::empty({x.size(1)}, gamma.options()),
-          at::empty({x.size(1)}, gamma.options()), at::empty_like(x, x.options().dtype(at::kBFloat16))};
-}
-std::tuple<Tensor, Tensor> gdn_fwd_rn_meta(const Tensor& x, const Tensor&, const Tensor&, bool, int64_t, bool xb) {
-  return {at::empty_like(x), xb ? at::empty_like(x, x.options().dtype(at::kBFloat16))
-                                : at::empty({0}, x.options().dtype(at::kBFloat16))};
+  GdnBwd o = gdn_bwd_out(x, gamma, true, Copy::Full);
+  return {o.dx, o.dg, o.dbeta, o.dxsum, o.dxb};
 }
 std::tuple<Tensor, Tensor, Tensor, Tensor, Tensor> gdn_bwd_sum_rn_meta(const Tensor& x, const Tensor&, const Tensor&,
                                                                        const Tensor& gamma, bool, int64_t, bool xb) {
-  return {at::empty_like(x), at::empty_like(gamma, at::MemoryFormat::Contiguous), at::empty({x.size(1)}, gamma.options()),
-          at::empty({x.size(1)}, gamma.options()),
-          xb ? at::empty_like(x, x.options().dtype(at::kBFloat16)) : at::empty({0}, x.options().dtype(at::kBFloat16))};
-}
-Tensor conv2d_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor& w, const c10::optional<Tensor>& b,
-                          int64_t stride, int64_t pad, int64_t act, int64_t math) {
-  return conv2d_fwd_meta(x, w, b, stride, pad, act, math);
-}
-Tensor conv_transpose2d_dgrad_xb_meta(const Tensor& dy, const Tensor&, const Tensor& w, const Tensor& x, int64_t s,
-                                      int64_t p, int64_t m) {
-  return conv_transpose2d_dgrad_meta(dy, w, x, s, p, m);
-}
-
-Tensor conv2d_dgrad_xb_meta(const Tensor& dy, const Tensor&, const Tensor& w, const Tensor& x, int64_t s, int64_t p,
-                            int64_t m) {
-  return conv2d_dgrad_meta(dy, w, x, s, p, m);
-}
-Tensor conv_transpose2d_fwd_xb_meta(const Tensor& x, const Tensor&, const Tensor& w, const c10::optional<Tensor>& b,
-                                    int64_t stride, int64_t pad, int64_t op, int64_t act, int64_t math) {
-  return conv_transpose2d_fwd_meta(x, w, b, stride, pad, op, act, math);
-}
-
-std::tuple<Tensor, Tensor> conv2d_wgrad_xb_meta(const Tensor& x, const Tensor&, const Tensor& dy, const Tensor&,
-                                                const Tensor& w, int64_t s, int64_t p, bool bias, int64_t m) {
-  return conv2d_wgrad_meta(x, dy, w, s, p, bias, m);
-}
-std::tuple<Tensor, Tensor> conv_transpose2d_wgrad_xb_meta(const Tensor& x, const Tensor&, const Tensor& dy,
-                                                          const Tensor&, const Tensor& w, int64_t s, int64_t p,
-                                                          bool bias, int64_t m) {
-  return conv_transpose2d_wgrad_meta(x, dy, w, s, p, bias, m);
+  GdnBwd o = gdn_bwd_out(x, gamma, true, xb ? Copy::Full : Copy::Empty);
+  return {o.dx, o.dg, o.dbeta, o.dxsum, o.dxb};
 }
 
 // elementwise / loss / entropy shape kernels
@@ -1140,19 +1012,41 @@ const unsigned char* codec_rows(const std::optional<Tensor>& rows, int64_t n) {
   return rows->data_ptr<unsigned char>();
 }
 
+// The four symbolizers (symbolize / symbolize_seg here, of imgcomp_stream and of imgcomp_mean): x, about mu where
+// given, to its symbols, as one run (seg false, nseg 1) or as nseg equal segments.  Returns sym and each
+// segment's largest magnitude; one over the coder's limit is a ValueError under the op's namespace `ns`.
+Tensor symbols_out(const Tensor& x) { return at::empty({x.numel()}, x.options().dtype(at::kInt)); }
+
+std::tuple<Tensor, std::vector<int64_t>> symbolize(const char* ns, const char* what, const Tensor& x, const Tensor* mu,
+                                                   bool seg, int64_t nseg) {
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor sym = symbols_out(x);
+  Tensor kd = at::empty({nseg}, x.options().dtype(at::kInt));
+  std::vector<int> kmax((size_t)nseg, 0);
+  const float* xp = x.data_ptr<float>();
+  const float* mp = mu ? mu->data_ptr<float>() : nullptr;
+  const int64_t n = x.numel();
+  int *sp = sym.data_ptr<int>(), *kp = kd.data_ptr<int>();
+  const int rc = seg ? (mu ? ic_codec_symbolize_mean_seg(xp, mp, (int)nseg, n / nseg, sp, kp, kmax.data(), stream_of(x))
+                           : ic_codec_symbolize_seg(xp, (int)nseg, n / nseg, sp, kp, kmax.data(), stream_of(x)))
+                     : (mu ? ic_codec_symbolize_mean(xp, mp, n, sp, kp, kmax.data(), stream_of(x))
+                           : ic_codec_symbolize(xp, n, sp, kp, kmax.data(), stream_of(x)));
+  if (rc == IC_ERR_ARG)
+    for (int64_t s = 0; s < nseg; ++s) {
+      TORCH_CHECK_VALUE(seg || kmax[s] <= IC_CODEC_KMAX, ns, ": a symbol of magnitude ", kmax[s],
+                        " exceeds the coder's limit of ", IC_CODEC_KMAX);
+      TORCH_CHECK_VALUE(kmax[s] <= IC_CODEC_KMAX, ns, ": image ", s, " has a symbol of magnitude ", kmax[s],
+                        ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+    }
+  check_rc(rc, what);
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
 std::tuple<Tensor, int64_t> codec_symbolize(const Tensor& x) {
   check_dense(x, "x");
   TORCH_CHECK(x.numel() > 0, "imgcomp_codec: empty tensor");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  Tensor sym = at::empty({x.numel()}, x.options().dtype(at::kInt));
-  Tensor kd = at::empty({1}, x.options().dtype(at::kInt));
-  int kmax = 0;
-  const int rc = ic_codec_symbolize(x.data_ptr<float>(), x.numel(), sym.data_ptr<int>(), kd.data_ptr<int>(), &kmax,
-                                    stream_of(x));
-  TORCH_CHECK_VALUE(!(rc == IC_ERR_ARG && kmax > IC_CODEC_KMAX), "imgcomp_codec: a symbol of magnitude ", kmax,
-                    " exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "codec_symbolize");
-  return {sym, (int64_t)kmax};
+  auto r = symbolize("imgcomp_codec", "codec_symbolize", x, nullptr, false, 1);
+  return {std::get<0>(r), std::get<1>(r)[0]};
 }
 
 Tensor codec_scale_index(const Tensor& sigma, at::ArrayRef<double> mids) {
@@ -1221,9 +1115,7 @@ Tensor codec_decode(const Tensor& packed, int64_t n, const std::optional<Tensor>
   return out;
 }
 
-std::tuple<Tensor, int64_t> codec_symbolize_meta(const Tensor& x) {
-  return {at::empty({x.numel()}, x.options().dtype(at::kInt)), 0};
-}
+std::tuple<Tensor, int64_t> codec_symbolize_meta(const Tensor& x) { return {symbols_out(x), 0}; }
 Tensor codec_scale_index_meta(const Tensor& sigma, at::ArrayRef<double>) {
   return at::empty({sigma.numel()}, sigma.options().dtype(at::kByte));
 }
@@ -1264,18 +1156,7 @@ std::tuple<Tensor, std::vector<int64_t>> stream_symbolize_seg(const Tensor& x, i
   check_dense(x, "x");
   TORCH_CHECK(nseg >= 1 && nseg <= 65535 && x.numel() > 0 && x.numel() % nseg == 0,
               "imgcomp_stream: ", x.numel(), " values do not make ", nseg, " equal segments");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
-  Tensor sym = at::empty({x.numel()}, x.options().dtype(at::kInt));
-  Tensor kd = at::empty({nseg}, x.options().dtype(at::kInt));
-  std::vector<int> kmax((size_t)nseg, 0);
-  const int rc = ic_codec_symbolize_seg(x.data_ptr<float>(), (int)nseg, x.numel() / nseg, sym.data_ptr<int>(),
-                                        kd.data_ptr<int>(), kmax.data(), stream_of(x));
-  if (rc == IC_ERR_ARG)
-    for (int64_t s = 0; s < nseg; ++s)
-      TORCH_CHECK_VALUE(kmax[s] <= IC_CODEC_KMAX, "imgcomp_stream: image ", s, " has a symbol of magnitude ", kmax[s],
-                        ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "codec_symbolize_seg");
-  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+  return symbolize("imgcomp_stream", "codec_symbolize_seg", x, nullptr, true, nseg);
 }
 
 // [lengths: all chunks x u32][payload], (segment, chunk) order, padded to the worst case
@@ -1354,7 +1235,7 @@ Tensor stream_crop_clamp(const Tensor& x, int64_t h, int64_t w) {
 }
 
 std::tuple<Tensor, std::vector<int64_t>> stream_symbolize_seg_meta(const Tensor& x, int64_t nseg) {
-  return {at::empty({x.numel()}, x.options().dtype(at::kInt)), std::vector<int64_t>((size_t)std::max<int64_t>(nseg, 0), 0)};
+  return {symbols_out(x), std::vector<int64_t>((size_t)std::max<int64_t>(nseg, 0), 0)};
 }
 Tensor stream_encode_seg_meta(const Tensor& sym, int64_t nseg, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t,
                               at::IntArrayRef, at::IntArrayRef, int64_t steps) {
@@ -1389,34 +1270,15 @@ void check_mean_pair(const Tensor& a, const Tensor& mu, const char* what) {
 
 std::tuple<Tensor, int64_t> mean_symbolize(const Tensor& y, const Tensor& mu) {
   check_mean_pair(y, mu, "y");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
-  Tensor sym = at::empty({y.numel()}, y.options().dtype(at::kInt));
-  Tensor kd = at::empty({1}, y.options().dtype(at::kInt));
-  int kmax = 0;
-  const int rc = ic_codec_symbolize_mean(y.data_ptr<float>(), mu.data_ptr<float>(), y.numel(), sym.data_ptr<int>(),
-                                         kd.data_ptr<int>(), &kmax, stream_of(y));
-  TORCH_CHECK_VALUE(!(rc == IC_ERR_ARG && kmax > IC_CODEC_KMAX), "imgcomp_mean: a symbol of magnitude ", kmax,
-                    " exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "codec_symbolize_mean");
-  return {sym, (int64_t)kmax};
+  auto r = symbolize("imgcomp_mean", "codec_symbolize_mean", y, &mu, false, 1);
+  return {std::get<0>(r), std::get<1>(r)[0]};
 }
 
 std::tuple<Tensor, std::vector<int64_t>> mean_symbolize_seg(const Tensor& y, const Tensor& mu, int64_t nseg) {
   check_mean_pair(y, mu, "y");
   TORCH_CHECK(nseg >= 1 && nseg <= 65535 && y.numel() % nseg == 0, "imgcomp_mean: ", y.numel(), " values do not make ",
               nseg, " equal segments");
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
-  Tensor sym = at::empty({y.numel()}, y.options().dtype(at::kInt));
-  Tensor kd = at::empty({nseg}, y.options().dtype(at::kInt));
-  std::vector<int> kmax((size_t)nseg, 0);
-  const int rc = ic_codec_symbolize_mean_seg(y.data_ptr<float>(), mu.data_ptr<float>(), (int)nseg, y.numel() / nseg,
-                                             sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(y));
-  if (rc == IC_ERR_ARG)
-    for (int64_t s = 0; s < nseg; ++s)
-      TORCH_CHECK_VALUE(kmax[s] <= IC_CODEC_KMAX, "imgcomp_mean: image ", s, " has a symbol of magnitude ", kmax[s],
-                        ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "codec_symbolize_mean_seg");
-  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+  return symbolize("imgcomp_mean", "codec_symbolize_mean_seg", y, &mu, true, nseg);
 }
 
 std::tuple<Tensor, Tensor> mean_center_round(const Tensor& y, const Tensor& mu) {
@@ -1441,11 +1303,11 @@ Tensor mean_add(const Tensor& r, const Tensor& mu) {
 
 std::tuple<Tensor, int64_t> mean_symbolize_meta(const Tensor& y, const Tensor& mu) {
   TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
-  return {at::empty({y.numel()}, y.options().dtype(at::kInt)), 0};
+  return {symbols_out(y), 0};
 }
 std::tuple<Tensor, std::vector<int64_t>> mean_symbolize_seg_meta(const Tensor& y, const Tensor& mu, int64_t nseg) {
   TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
-  return {at::empty({y.numel()}, y.options().dtype(at::kInt)), std::vector<int64_t>((size_t)std::max<int64_t>(nseg, 0), 0)};
+  return stream_symbolize_seg_meta(y, nseg);
 }
 std::tuple<Tensor, Tensor> mean_center_round_meta(const Tensor& y, const Tensor& mu) {
   TORCH_CHECK(y.numel() == mu.numel(), "imgcomp_mean: y and mu must hold the same number of values");
@@ -1676,7 +1538,9 @@ TORCH_LIBRARY(imgcomp, m) {
         "bool need_img2) -> (Tensor, Tensor)");
 }
 
-TORCH_LIBRARY_IMPL(imgcomp, CUDA, m) {  // the CUDA dispatch key is PyTorch-ROCm's HIP device key
+// The conv / GDN launchers are registered for CPU tensors as well, which their operand checks refuse by name
+// ("x must be on a ROCm device"): there is no CPU path, and the launcher says so itself.
+static void impl_conv_gdn(torch::Library& m) {
   m.impl("conv2d_fwd", conv2d_fwd);
   m.impl("conv2d_fwd_ws", conv2d_fwd_ws);
   m.impl("conv_transpose2d_fwd_ws", conv_transpose2d_fwd_ws);
@@ -1698,6 +1562,12 @@ TORCH_LIBRARY_IMPL(imgcomp, CUDA, m) {  // the CUDA dispatch key is PyTorch-ROCm
   m.impl("conv2d_wgrad_xb", conv2d_wgrad_xb);
   m.impl("conv_transpose2d_wgrad_xb", conv_transpose2d_wgrad_xb);
   m.impl("conv_transpose2d_fwd_xb", conv_transpose2d_fwd_xb);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp, CPU, m) { impl_conv_gdn(m); }
+
+TORCH_LIBRARY_IMPL(imgcomp, CUDA, m) {  // the CUDA dispatch key is PyTorch-ROCm's HIP device key
+  impl_conv_gdn(m);
   m.impl("nonneg_fwd", nonneg_fwd);
   m.impl("nonneg_bwd", nonneg_bwd);
   m.impl("nonneg_multi_fwd", nonneg_multi_fwd);
@@ -1732,11 +1602,11 @@ TORCH_LIBRARY_IMPL(imgcomp, Meta, m) {
   m.impl("conv2d_fwd", conv2d_fwd_meta);
   m.impl("conv2d_fwd_ws", conv2d_fwd_ws_meta);
   m.impl("conv_transpose2d_fwd_ws", conv_transpose2d_fwd_ws_meta);
-  m.impl("conv2d_dgrad", conv2d_dgrad_meta);
-  m.impl("conv2d_wgrad", conv2d_wgrad_meta);
+  m.impl("conv2d_dgrad", conv_dgrad_meta<true>);
+  m.impl("conv2d_wgrad", conv_wgrad_meta<false>);
   m.impl("conv_transpose2d_fwd", conv_transpose2d_fwd_meta);
-  m.impl("conv_transpose2d_dgrad", conv_transpose2d_dgrad_meta);
-  m.impl("conv_transpose2d_wgrad", conv_transpose2d_wgrad_meta);
+  m.impl("conv_transpose2d_dgrad", conv_dgrad_meta<false>);
+  m.impl("conv_transpose2d_wgrad", conv_wgrad_meta<true>);
   m.impl("gdn_fwd", gdn_fwd_meta);
   m.impl("gdn_bwd", gdn_bwd_meta);
   m.impl("gdn_bwd_sum", gdn_bwd_sum_meta);
@@ -1745,10 +1615,10 @@ TORCH_LIBRARY_IMPL(imgcomp, Meta, m) {
   m.impl("gdn_fwd_rn", gdn_fwd_rn_meta);
   m.impl("gdn_bwd_sum_rn", gdn_bwd_sum_rn_meta);
   m.impl("conv2d_fwd_xb", conv2d_fwd_xb_meta);
-  m.impl("conv_transpose2d_dgrad_xb", conv_transpose2d_dgrad_xb_meta);
-  m.impl("conv2d_dgrad_xb", conv2d_dgrad_xb_meta);
-  m.impl("conv2d_wgrad_xb", conv2d_wgrad_xb_meta);
-  m.impl("conv_transpose2d_wgrad_xb", conv_transpose2d_wgrad_xb_meta);
+  m.impl("conv_transpose2d_dgrad_xb", conv_dgrad_xb_meta);
+  m.impl("conv2d_dgrad_xb", conv_dgrad_xb_meta);
+  m.impl("conv2d_wgrad_xb", conv_wgrad_xb_meta<false>);
+  m.impl("conv_transpose2d_wgrad_xb", conv_wgrad_xb_meta<true>);
   m.impl("conv_transpose2d_fwd_xb", conv_transpose2d_fwd_xb_meta);
   m.impl("nonneg_fwd", nonneg_fwd_meta);
   m.impl("nonneg_bwd", nonneg_bwd_meta);

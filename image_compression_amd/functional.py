@@ -95,28 +95,41 @@ def _log_plan(op, a, b, k=1, stride=1, pad=0, math=0):
 # between (or any other tensor) falls back to the pass.  Backward passes of several devices may
 # run concurrently (one autograd thread per device; nn.DataParallel replicas), so the table is
 # locked.
-_COLSUMS = {}
-_COLSUMS_LOCK = threading.Lock()
+class _Handoff:
+    """Payloads handed from the op that produced a tensor to the op that receives it (see above, and the
+    bf16 copies below): put(t, payload), then take(t) once, by the same tensor at the same version."""
 
+    def __init__(self):
+        self._entries = {}
+        self._lock = threading.Lock()
+        self.stats = {"put": 0, "hit": 0}
 
-def _colsum_key(t):
-    return (t.device.index, t.data_ptr())
+    @staticmethod
+    def _key(t):
+        return (t.device.index, t.data_ptr())
 
+    def put(self, t, payload):
+        with self._lock:
+            for k in [k for k, (r, _, _) in self._entries.items() if r() is None]:
+                del self._entries[k]
+            self._entries[self._key(t)] = (weakref.ref(t), t._version, payload)
+            self.stats["put"] += 1
 
-def _put_colsum(t, s):
-    with _COLSUMS_LOCK:
-        for k in [k for k, (r, _, _) in _COLSUMS.items() if r() is None]:
-            del _COLSUMS[k]
-        _COLSUMS[_colsum_key(t)] = (weakref.ref(t), t._version, s)
-
-
-def _take_colsum(t):
-    with _COLSUMS_LOCK:
-        e = _COLSUMS.pop(_colsum_key(t), None)
-    if e is None:
+    def take(self, t, fits=None):
+        """The payload put for t, or None; fits(payload): a further condition of a hit."""
+        with self._lock:
+            e = self._entries.pop(self._key(t), None)
+        if e is None:
+            return None
+        r, ver, payload = e
+        if r() is t and t._version == ver and (fits is None or fits(payload)):
+            self.stats["hit"] += 1
+            return payload
         return None
-    r, ver, s = e
-    return s if (r() is t and t._version == ver) else None
+
+
+_COLSUMS = _Handoff()
+_put_colsum, _take_colsum = _COLSUMS.put, _COLSUMS.take
 
 
 # ---------------------------------------------------------- bf16 activation copies (config C3)
@@ -125,136 +138,96 @@ def _take_colsum(t):
 # NHWC bf16 copy in the same kernel (torch.ops.imgcomp.gdn_fwd_xb / gdn_bwd_sum_xb) and leaves it
 # here, keyed like the column sums above; the consuming conv takes it (conv2d_fwd_xb /
 # conv_transpose2d_dgrad_xb) and reads 2 B per element instead of converting the fp32 tensor.
-_BF16 = {}
-_BF16_LOCK = threading.Lock()
-BF16_COPY_STATS = {"put": 0, "hit": 0}
-
-
-def _put_bf16(t, tb):
-    with _BF16_LOCK:
-        for k in [k for k, (r, _, _) in _BF16.items() if r() is None]:
-            del _BF16[k]
-        _BF16[_colsum_key(t)] = (weakref.ref(t), t._version, tb)
-        BF16_COPY_STATS["put"] += 1
+_BF16 = _Handoff()
+BF16_COPY_STATS = _BF16.stats
+_put_bf16 = _BF16.put
 
 
 def _take_bf16(t):
-    with _BF16_LOCK:
-        e = _BF16.pop(_colsum_key(t), None)
-    if e is None:
-        return None
-    r, ver, tb = e
-    if r() is t and t._version == ver and tb.shape == t.shape and tb.stride() == t.stride():
-        BF16_COPY_STATS["hit"] += 1
-        return tb
-    return None
+    return _BF16.take(t, lambda tb: tb.shape == t.shape and tb.stride() == t.stride())
+
+
+# torch.nn.Conv2d (analysis.py:55, prior_analysis.py:54-56) and torch.nn.ConvTranspose2d (synthesis.py:55-57,
+# prior_synthesis.py:54-56): one forward and one backward for both, each launch one torch.ops.imgcomp op
+# (csrc/torch_ops.cpp -> C ABI).  A transposed conv differs in its ops' names, in the weight dimension that
+# matches the input's channels (0, not 1), and in taking an output_padding after stride and padding.
+_CONV_OP = {False: "conv2d", True: "conv_transpose2d"}
+
+
+def _conv_forward(ctx, transposed, x, weight, bias, geom, act, math):
+    _lib.require_device(x, weight, bias)
+    x = _cl(x)
+    w = weight.contiguous()
+    b = None if bias is None else bias.contiguous()
+    op = _CONV_OP[transposed]
+    if w.shape[0 if transposed else 1] != x.shape[1] or w.shape[2] != w.shape[3]:
+        raise RuntimeError(f"{op}: weight {tuple(w.shape)} does not match input {tuple(x.shape)}")
+    xb = _take_bf16(x) if int(math) & MATH["bf16"] else None
+    if xb is not None:
+        y = getattr(_lib.ops(), op + "_fwd_xb")(x, xb, w, b, *geom, int(act), int(math))
+    else:
+        y = getattr(_lib.ops(), op + "_fwd")(x, w, b, *geom, int(act), int(math))
+    stride, padding = geom[:2]
+    _log_plan(op + "_fwd", x, y, w.shape[2], stride, padding, math)
+    # x's bf16 copy, for the weight gradient with dy's (*_wgrad_xb); held to the backward
+    # (2 B per element of x) only when that weight gradient will run
+    ctx.xb = xb if ctx.needs_input_grad[1] else None
+    ctx.conf = (stride, padding, act, b is not None, int(math))
+    ctx.save_for_backward(x, w, y if act else None)
+    return y
+
+
+def _conv_backward(ctx, transposed, gy):
+    """(dx, dw, db)"""
+    x, w, y = ctx.saved_tensors
+    stride, padding, act, has_b, math = ctx.conf
+    # the bias gradient formed by gy's producer (taken only where this node owns the bias gradient)
+    pre = _take_colsum(gy) if (has_b and not act and ctx.needs_input_grad[2]) else None
+    gyb = _take_bf16(gy) if (math & MATH["bf16"]) and not act else None
+    if act:
+        gy = relu_bwd(y, gy)
+    gy = _cl(gy)
+    dx = dw = db = None
+    ops, op, k = _lib.ops(), _CONV_OP[transposed], w.shape[2]
+    if ctx.needs_input_grad[0]:
+        if gyb is not None and gyb.stride() == gy.stride():
+            dx = getattr(ops, op + "_dgrad_xb")(gy, gyb, w, x, stride, padding, math)
+        else:
+            dx = getattr(ops, op + "_dgrad")(gy, w, x, stride, padding, math)
+        _log_plan(op + "_dgrad", gy, dx, k, stride, padding, math)
+    if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
+        xb, ctx.xb = ctx.xb, None
+        if xb is not None and gyb is not None and gyb.stride() == gy.stride():
+            dw, db = getattr(ops, op + "_wgrad_xb")(x, xb, gy, gyb, w, stride, padding, has_b and pre is None, math)
+        else:
+            dw, db = getattr(ops, op + "_wgrad")(x, gy, w, stride, padding, has_b and pre is None, math)
+        _log_plan(op + "_wgrad", x, gy, k, stride, padding, math)
+        db = (db if pre is None else pre) if has_b else None
+    return dx, dw, db
 
 
 class Conv2dFn(Function):
-    """torch.nn.Conv2d forward/backward (analysis.py:55, prior_analysis.py:54-56), each
-    launch one torch.ops.imgcomp op (csrc/torch_ops.cpp -> C ABI)."""
+    transposed = False
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, act, math=0):
-        _lib.require_device(x, weight, bias)
-        x = _cl(x)
-        w = weight.contiguous()
-        b = None if bias is None else bias.contiguous()
-        if w.shape[1] != x.shape[1] or w.shape[2] != w.shape[3]:
-            raise RuntimeError(f"conv2d: weight {tuple(w.shape)} does not match input {tuple(x.shape)}")
-        xb = _take_bf16(x) if int(math) & MATH["bf16"] else None
-        if xb is not None:
-            y = _lib.ops().conv2d_fwd_xb(x, xb, w, b, stride, padding, int(act), int(math))
-        else:
-            y = _lib.ops().conv2d_fwd(x, w, b, stride, padding, int(act), int(math))
-        _log_plan("conv2d_fwd", x, y, w.shape[2], stride, padding, math)
-        # x's bf16 copy, for the weight gradient with dy's (conv2d_wgrad_xb); held to the backward
-        # (2 B per element of x) only when that weight gradient will run
-        ctx.xb = xb if ctx.needs_input_grad[1] else None
-        ctx.conf = (stride, padding, act, b is not None, int(math))
-        ctx.save_for_backward(x, w, y if act else None)
-        return y
+        return _conv_forward(ctx, False, x, weight, bias, (stride, padding), act, math)
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, padding, act, has_b, math = ctx.conf
-        # the bias gradient formed by gy's producer (taken only where this node owns the bias gradient)
-        pre = _take_colsum(gy) if (has_b and not act and ctx.needs_input_grad[2]) else None
-        gyb = _take_bf16(gy) if (math & MATH["bf16"]) and not act else None
-        if act:
-            gy = relu_bwd(y, gy)
-        gy = _cl(gy)
-        dx = dw = db = None
-        ops, k = _lib.ops(), w.shape[2]
-        if ctx.needs_input_grad[0]:
-            if gyb is not None and gyb.stride() == gy.stride():
-                dx = ops.conv2d_dgrad_xb(gy, gyb, w, x, stride, padding, math)
-            else:
-                dx = ops.conv2d_dgrad(gy, w, x, stride, padding, math)
-            _log_plan("conv2d_dgrad", gy, dx, k, stride, padding, math)
-        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
-            xb, ctx.xb = ctx.xb, None
-            if xb is not None and gyb is not None and gyb.stride() == gy.stride():
-                dw, db = ops.conv2d_wgrad_xb(x, xb, gy, gyb, w, stride, padding, has_b and pre is None, math)
-            else:
-                dw, db = ops.conv2d_wgrad(x, gy, w, stride, padding, has_b and pre is None, math)
-            _log_plan("conv2d_wgrad", x, gy, k, stride, padding, math)
-            db = (db if pre is None else pre) if has_b else None
-        return dx, dw, db, None, None, None, None
+        return _conv_backward(ctx, False, gy) + (None,) * 4
 
 
 class ConvTranspose2dFn(Function):
-    """torch.nn.ConvTranspose2d forward/backward (synthesis.py:55-57, prior_synthesis.py:54-56)."""
+    transposed = True
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, padding, output_padding, act, math=0):
-        _lib.require_device(x, weight, bias)
-        x = _cl(x)
-        w = weight.contiguous()
-        b = None if bias is None else bias.contiguous()
-        if w.shape[0] != x.shape[1] or w.shape[2] != w.shape[3]:
-            raise RuntimeError(f"conv_transpose2d: weight {tuple(w.shape)} does not match input {tuple(x.shape)}")
-        xb = _take_bf16(x) if int(math) & MATH["bf16"] else None
-        if xb is not None:
-            y = _lib.ops().conv_transpose2d_fwd_xb(x, xb, w, b, stride, padding, output_padding, int(act), int(math))
-        else:
-            y = _lib.ops().conv_transpose2d_fwd(x, w, b, stride, padding, output_padding, int(act), int(math))
-        _log_plan("conv_transpose2d_fwd", x, y, w.shape[2], stride, padding, math)
-        # x's bf16 copy, for the weight gradient with dy's (conv_transpose2d_wgrad_xb); held to the backward
-        # (2 B per element of x) only when that weight gradient will run
-        ctx.xb = xb if ctx.needs_input_grad[1] else None
-        ctx.conf = (stride, padding, act, b is not None, int(math))
-        ctx.save_for_backward(x, w, y if act else None)
-        return y
+        return _conv_forward(ctx, True, x, weight, bias, (stride, padding, output_padding), act, math)
 
     @staticmethod
     def backward(ctx, gy):
-        x, w, y = ctx.saved_tensors
-        stride, padding, act, has_b, math = ctx.conf
-        # the bias gradient formed by gy's producer (taken only where this node owns the bias gradient)
-        pre = _take_colsum(gy) if (has_b and not act and ctx.needs_input_grad[2]) else None
-        gyb = _take_bf16(gy) if (math & MATH["bf16"]) and not act else None
-        if act:
-            gy = relu_bwd(y, gy)
-        gy = _cl(gy)
-        dx = dw = db = None
-        ops, k = _lib.ops(), w.shape[2]
-        if ctx.needs_input_grad[0]:
-            if gyb is not None and gyb.stride() == gy.stride():
-                dx = ops.conv_transpose2d_dgrad_xb(gy, gyb, w, x, stride, padding, math)
-            else:
-                dx = ops.conv_transpose2d_dgrad(gy, w, x, stride, padding, math)
-            _log_plan("conv_transpose2d_dgrad", gy, dx, k, stride, padding, math)
-        if ctx.needs_input_grad[1] or (has_b and ctx.needs_input_grad[2]):
-            xb, ctx.xb = ctx.xb, None
-            if xb is not None and gyb is not None and gyb.stride() == gy.stride():
-                dw, db = ops.conv_transpose2d_wgrad_xb(x, xb, gy, gyb, w, stride, padding, has_b and pre is None, math)
-            else:
-                dw, db = ops.conv_transpose2d_wgrad(x, gy, w, stride, padding, has_b and pre is None, math)
-            _log_plan("conv_transpose2d_wgrad", x, gy, k, stride, padding, math)
-            db = (db if pre is None else pre) if has_b else None
-        return dx, dw, db, None, None, None, None, None
+        return _conv_backward(ctx, True, gy) + (None,) * 5
 
 
 # include/imgcomp.h IC_MATH_*: "fp32" exact fp32 MFMA; "bf16" bf16 operands, fp32 accumulation
@@ -403,14 +376,9 @@ class _ConvWGradFn(Function):
             ctx.holder["y"].record_stream(cur)
         gy = relu_bwd(ctx.holder["y"], gz) if act else gz
         gy = _cl(gy)
-        ops, k = _lib.ops(), w.shape[2]
-        fb = ctx.has_b and pre is None
-        if transposed:
-            dw, db = ops.conv_transpose2d_wgrad(x, gy, w, stride, padding, fb, math)
-            _log_plan("conv_transpose2d_wgrad", x, gy, k, stride, padding, math)
-        else:
-            dw, db = ops.conv2d_wgrad(x, gy, w, stride, padding, fb, math)
-            _log_plan("conv2d_wgrad", x, gy, k, stride, padding, math)
+        op = _CONV_OP[transposed] + "_wgrad"
+        dw, db = getattr(_lib.ops(), op)(x, gy, w, stride, padding, ctx.has_b and pre is None, math)
+        _log_plan(op, x, gy, w.shape[2], stride, padding, math)
         return None, dw, ((db if pre is None else pre) if ctx.has_b else None), None, None, None
 
 
@@ -437,36 +405,31 @@ def _deferred_wgrad(ws, data_fn, x, weight, bias, args, conf, shape):
     return _JoinFn.apply(y, z)
 
 
+def _conv(fn, x, weight, bias, geom, act, math, cout, out):
+    """The three ways a conv runs.  fn: Conv2dFn / ConvTranspose2dFn; geom: (stride, padding) and, transposed,
+    output_padding; cout and out(n): the output's channels and its height / width from the input's."""
+    if _wcache_on(x):
+        return _cached_conv(_CONV_OP[fn.transposed] + "_fwd_ws", x, weight, bias, geom + (act,), math)
+    ws = _wgrad_stream(x, weight)
+    if ws is not None:
+        shape = (x.shape[0], cout, out(x.shape[2]), out(x.shape[3]))
+        return _deferred_wgrad(ws, fn, x, weight, bias, geom + (act, math),
+                               (fn.transposed, geom[0], geom[1], act, math), shape)
+    return fn.apply(x, weight, bias, *geom, act, math)
+
+
 def conv2d(x, weight, bias=None, stride=1, padding=0, act=0, math=0):
     """`math` (forward and input gradient): 0 fp32 (default), 1 bf16 operands with fp32
     accumulation, 2 fp32 by exact bf16 split (see MATH)."""
-    if _wcache_on(x):
-        return _cached_conv("conv2d_fwd_ws", x, weight, bias, (int(stride), int(padding), int(act)), math)
-    ws = _wgrad_stream(x, weight)
-    if ws is not None:
-        k = weight.shape[2]
-        N, _, H, W = x.shape
-        shape = (N, weight.shape[0], (H + 2 * padding - k) // stride + 1, (W + 2 * padding - k) // stride + 1)
-        return _deferred_wgrad(ws, Conv2dFn, x, weight, bias, (int(stride), int(padding), int(act), int(math)),
-                               (False, int(stride), int(padding), int(act), int(math)), shape)
-    return Conv2dFn.apply(x, weight, bias, int(stride), int(padding), int(act), int(math))
+    k = weight.shape[2]
+    return _conv(Conv2dFn, x, weight, bias, (int(stride), int(padding)), int(act), int(math), weight.shape[0],
+                 lambda n: (n + 2 * padding - k) // stride + 1)
 
 
 def conv_transpose2d(x, weight, bias=None, stride=1, padding=0, output_padding=0, act=0, math=0):
-    if _wcache_on(x):
-        return _cached_conv("conv_transpose2d_fwd_ws", x, weight, bias,
-                            (int(stride), int(padding), int(output_padding), int(act)), math)
-    ws = _wgrad_stream(x, weight)
-    if ws is not None:
-        k = weight.shape[2]
-        N, _, H, W = x.shape
-        shape = (N, weight.shape[1], (H - 1) * stride - 2 * padding + k + output_padding,
-                 (W - 1) * stride - 2 * padding + k + output_padding)
-        return _deferred_wgrad(ws, ConvTranspose2dFn, x, weight, bias,
-                               (int(stride), int(padding), int(output_padding), int(act), int(math)),
-                               (True, int(stride), int(padding), int(act), int(math)), shape)
-    return ConvTranspose2dFn.apply(x, weight, bias, int(stride), int(padding), int(output_padding), int(act),
-                                   int(math))
+    k = weight.shape[2]
+    return _conv(ConvTranspose2dFn, x, weight, bias, (int(stride), int(padding), int(output_padding)), int(act),
+                 int(math), weight.shape[1], lambda n: (n - 1) * stride - 2 * padding + k + output_padding)
 
 
 # ============================================================== GDN

@@ -369,6 +369,137 @@ def test_every_registered_op_has_a_meta_kernel():
                 assert tuple(t.shape) == tuple(shp), (name, tuple(t.shape), shp)
 
 
+OP_NAMESPACES = ("imgcomp", "imgcomp_codec", "imgcomp_stream", "imgcomp_mean", "imgcomp_ckbd")
+
+
+def test_op_surface_is_the_recorded_one():
+    """Every op of the five namespaces has exactly the schema recorded in tests/golden/op_schemas.txt (taken
+    from the build before the conv / GDN / symbolizer launchers were folded), and no op has
+    vanished or appeared: tests and tools call these ops by name and position."""
+    from image_compression_amd import _lib
+    _lib.ops()
+    recorded = open(os.path.join(ROOT, "tests", "golden", "op_schemas.txt")).read().split("\n")[:-1]
+    assert len(recorded) == len(set(recorded)) == 69
+    by_name = {line.split("(")[0]: line for line in recorded}
+    registered = {n for n in torch._C._dispatch_get_all_op_names() if n.split("::")[0] in OP_NAMESPACES}
+    assert registered == set(by_name), sorted(registered ^ set(by_name))   # overloads would show up as name.overload
+    for name, line in by_name.items():
+        ns, op = name.split("::")
+        assert str(getattr(getattr(torch.ops, ns), op).default._schema) == line, name
+
+
+CONTIG, CHLAST = "contiguous", "channels_last"
+
+
+def _layout(t):
+    """(dtype, memory format) of an output; the format of a 4-D tensor only where the two differ."""
+    if t.dim() != 4 or t.is_contiguous() == t.is_contiguous(memory_format=torch.channels_last):
+        return t.dtype, None
+    return t.dtype, CONTIG if t.is_contiguous() else CHLAST
+
+
+# conv / GDN op (a key of _meta_cases, or a further call) -> (dtype, memory format) of each output, as the build
+# before the launchers were folded returned them (DESIGN.md 11e)
+def _meta_layout_cases():
+    f32, bf16 = torch.float32, torch.bfloat16
+    x = _meta(2, 192, 16, 16, cl=True)
+    xb = _meta(2, 192, 16, 16, cl=True, dtype=bf16)
+    y, yb = _meta(2, 192, 8, 8, cl=True), _meta(2, 192, 8, 8, cl=True, dtype=bf16)
+    w, g, b = _meta(192, 192, 5, 5), _meta(192, 192), _meta(192)
+    ws = _meta(16, dtype=torch.uint8)
+    act, par, cpy = (f32, CHLAST), (f32, None), (bf16, CHLAST)
+    dw = (f32, CONTIG)
+    cases = {name: (call, [act]) for name, (call, _) in _meta_cases().items()
+             if name.startswith("conv") and "wgrad" not in name}
+    cases.update({name: (call, [dw, par]) for name, (call, _) in _meta_cases().items() if "wgrad" in name})
+    cases.update({
+        "gdn_fwd": (lambda o: o.gdn_fwd(x, g, b, False, 2), [act, act]),
+        "gdn_bwd": (lambda o: o.gdn_bwd(x, x, x, g, False, 2), [act, par, par]),
+        "gdn_bwd_sum": (lambda o: o.gdn_bwd_sum(x, x, x, g, False, 2), [act, par, par, par]),
+        # the variants that take or return a bf16 copy, or take a workspace
+        "gdn_fwd_xb": (lambda o: o.gdn_fwd_xb(x, g, b, False, 3), [act, act, cpy]),
+        "gdn_bwd_sum_xb": (lambda o: o.gdn_bwd_sum_xb(x, x, x, g, False, 3), [act, par, par, par, cpy]),
+        "gdn_fwd_rn": (lambda o: o.gdn_fwd_rn(x, g, b, False, 3, True), [act, cpy]),
+        "gdn_fwd_rn no copy": (lambda o: o.gdn_fwd_rn(x, g, b, False, 3, False), [act, (bf16, None, (0,))]),
+        "gdn_bwd_sum_rn": (lambda o: o.gdn_bwd_sum_rn(x, b, x, g, False, 3, True), [act, par, par, par, cpy]),
+        "gdn_bwd_sum_rn no copy": (lambda o: o.gdn_bwd_sum_rn(x, b, x, _meta(192, 192, 1, 1), False, 3, False),
+                                   [act, (f32, None, (192, 192, 1, 1)), par, par, (bf16, None, (0,))]),
+        "conv2d_fwd_ws": (lambda o: o.conv2d_fwd_ws(x, w, None, 2, 2, 0, 2, ws), [act + ((2, 192, 8, 8),)]),
+        "conv2d_fwd_xb": (lambda o: o.conv2d_fwd_xb(x, xb, w, None, 2, 2, 0, 3), [act + ((2, 192, 8, 8),)]),
+        "conv_transpose2d_fwd_ws": (lambda o: o.conv_transpose2d_fwd_ws(y, w, None, 2, 2, 1, 0, 2, ws),
+                                    [act + ((2, 192, 16, 16),)]),
+        "conv_transpose2d_fwd_xb": (lambda o: o.conv_transpose2d_fwd_xb(y, yb, w, None, 2, 2, 1, 0, 3),
+                                    [act + ((2, 192, 16, 16),)]),
+        # few output channels: contiguous (NCHW)
+        "conv2d_fwd to 3": (lambda o: o.conv2d_fwd(x, _meta(3, 192, 5, 5), None, 2, 2, 0, 2),
+                            [(f32, CONTIG, (2, 3, 8, 8))]),
+        "conv_transpose2d_fwd to 3": (lambda o: o.conv_transpose2d_fwd(y, _meta(192, 3, 5, 5), None, 2, 2, 1, 0, 2),
+                                      [(f32, CONTIG, (2, 3, 16, 16))]),
+        # the bias gradient has the weight's output dimension: 1 of a transposed conv's, 0 of a conv's
+        "conv_transpose2d_wgrad 32 -> 64": (lambda o: o.conv_transpose2d_wgrad(
+            _meta(2, 32, 8, 8, cl=True), _meta(2, 64, 16, 16, cl=True), _meta(32, 64, 5, 5), 2, 2, True, 2),
+                                            [dw + ((32, 64, 5, 5),), par + ((64,),)]),
+        "conv_transpose2d_wgrad_xb 32 -> 64": (lambda o: o.conv_transpose2d_wgrad_xb(
+            _meta(2, 32, 8, 8, cl=True), _meta(2, 32, 8, 8, cl=True, dtype=bf16), _meta(2, 64, 16, 16, cl=True),
+            _meta(2, 64, 16, 16, cl=True, dtype=bf16), _meta(32, 64, 5, 5), 2, 2, True, 3),
+                                               [dw + ((32, 64, 5, 5),), par + ((64,),)]),
+        "conv2d_wgrad 32 -> 64": (lambda o: o.conv2d_wgrad(
+            _meta(2, 32, 16, 16, cl=True), _meta(2, 64, 8, 8, cl=True), _meta(64, 32, 5, 5), 2, 2, True, 2),
+                                  [dw + ((64, 32, 5, 5),), par + ((64,),)]),
+        "conv2d_wgrad no bias": (lambda o: o.conv2d_wgrad(x, y, w, 2, 2, False, 2), [dw, par + ((0,),)]),
+        # dx: the memory format of x
+        "conv2d_dgrad onto the image": (lambda o: o.conv2d_dgrad(_meta(2, 192, 32, 32, cl=True), _meta(192, 3, 5, 5),
+                                                                 _meta(2, 3, 64, 64), 2, 2, 2),
+                                        [(f32, CONTIG, (2, 3, 64, 64))]),
+        "conv2d_dgrad onto 192 channels": (lambda o: o.conv2d_dgrad(y, w, x, 2, 2, 2), [act + ((2, 192, 16, 16),)]),
+    })
+    return cases
+
+
+def test_conv_gdn_meta_kernels_infer_dtype_and_memory_format():
+    """The shape kernels of the conv / GDN ops give every output the dtype and memory format the launchers
+    allocate: a bf16 copy has x's strides, a copy or bias gradient that is not produced is an empty (0,)
+    placeholder, dx has x's memory format."""
+    from image_compression_amd import _lib
+    ops = _lib.ops()
+    cases = _meta_layout_cases()
+    family = {n for n in _meta_cases() if n.startswith(("conv", "gdn"))}
+    assert len(family) == 21 and family <= set(cases), sorted(family - set(cases))
+    x = _meta(2, 192, 16, 16, cl=True)
+    for name, (call, expect) in cases.items():
+        out = call(ops)
+        out = out if isinstance(out, tuple) else (out,)
+        assert len(out) == len(expect), name
+        for t, e in zip(out, expect):
+            assert _layout(t) == tuple(e[:2]), (name, _layout(t), e)
+            if len(e) > 2:
+                assert tuple(t.shape) == e[2], (name, tuple(t.shape), e)
+            if t.dtype == torch.bfloat16 and t.numel():
+                assert t.shape == x.shape and t.stride() == x.stride(), name
+
+
+def test_conv_gdn_ops_refuse_cpu_tensors():
+    """Every conv / GDN launcher checks its operands before it reads a pointer: the forwards always did, the
+    gradients and the GDN backwards since they share one launcher per family."""
+    from image_compression_amd import _lib
+    ops = _lib.ops()
+    x, y = torch.zeros(1, 32, 8, 8), torch.zeros(1, 32, 8, 8)
+    w, g, b = torch.zeros(32, 32, 3, 3), torch.zeros(32, 32), torch.zeros(32)
+    calls = {
+        "conv2d_fwd": lambda: ops.conv2d_fwd(x, w, None, 1, 1, 0, 0),
+        "conv2d_dgrad": lambda: ops.conv2d_dgrad(y, w, x, 1, 1, 0),
+        "conv2d_wgrad": lambda: ops.conv2d_wgrad(x, y, w, 1, 1, True, 0),
+        "conv_transpose2d_fwd": lambda: ops.conv_transpose2d_fwd(x, w, None, 1, 1, 0, 0, 0),
+        "conv_transpose2d_dgrad": lambda: ops.conv_transpose2d_dgrad(y, w, x, 1, 1, 0),
+        "conv_transpose2d_wgrad": lambda: ops.conv_transpose2d_wgrad(x, y, w, 1, 1, True, 0),
+        "gdn_fwd": lambda: ops.gdn_fwd(x, g, b, False, 0),
+        "gdn_bwd_sum": lambda: ops.gdn_bwd_sum(x, x, y, g, False, 0),
+    }
+    for name, call in calls.items():
+        with pytest.raises(RuntimeError, match="must be on a ROCm device"):
+            call()
+
+
 def test_training_step_path_has_no_ctypes_call():
     """functional.py (the autograd Functions of the training step) dispatches every launch
     through torch.ops.imgcomp; the ctypes binding stays for the non-torch C ABI users."""

@@ -98,6 +98,58 @@ def test_conv_transpose2d_fwd_bwd(case):
     _check_grads([("dx", xd.grad, xr.grad), ("dw", wd.grad, wr.grad), ("db", bd.grad, br.grad)])
 
 
+@pytest.mark.parametrize("math_name", ["fp32", "fp32_split"])
+@pytest.mark.parametrize("transposed", [False, True])
+def test_conv_kinds_unequal_channels_and_routed_wgrad(transposed, math_name):
+    """Both kinds of conv run one forward and one backward (functional._conv_forward / _conv_backward) that
+    differ in the weight dimension they read: 32 -> 64 channels, so a swapped dimension cannot pass.  Stride 2,
+    bias, fused ReLU: the output and the three gradients against the fp64 oracle, and bitwise the same four
+    tensors with the weight gradient routed to a stream of its own (_ConvWGradFn)."""
+    s, p, k = 2, 2, 5
+    x = _rand(2, 32, 8, 8, seed=31)
+    w = _rand(*((32, 64) if transposed else (64, 32)), k, k, seed=32, scale=1.0 / math.sqrt(32 * k * k))
+    b = _rand(64, seed=33, scale=0.1)
+    xr, wr, br = (t.double().requires_grad_(True) for t in (x, w, b))
+    if transposed:
+        pre = F.conv_transpose2d(xr, wr, br, stride=s, padding=p, output_padding=1)
+    else:
+        pre = F.conv2d(xr, wr, br, stride=s, padding=p)
+    assert pre.shape == ((2, 64, 16, 16) if transposed else (2, 64, 4, 4))
+    gy = _rand(*pre.shape, seed=34)
+
+    def run():
+        xd, wd, bd = _to_dev(x, cl=True), _to_dev(w), _to_dev(b)
+        # x enters the graph here, on this stream, as an activation does in the model (exact: times one); a leaf
+        # would enter it through the routed weight-gradient node, on that node's stream
+        xin = xd * 1.0
+        if transposed:
+            y = IF.conv_transpose2d(xin, wd, bd, s, p, 1, act=1, math=IF.MATH[math_name])
+        else:
+            y = IF.conv2d(xin, wd, bd, s, p, act=1, math=IF.MATH[math_name])
+        y.backward(gy.to(DEV))
+        torch.cuda.synchronize()
+        return y.detach(), xd.grad, wd.grad, bd.grad
+
+    y, dx, dw, db = run()
+    # the ReLU's gradient mask is the device's (it may differ from the oracle's only on a tie, as in smoke())
+    mask = (y > 0).cpu()
+    off = mask != (pre.detach() > 0)
+    assert not off.any() or float(pre.detach()[off].abs().max()) <= 1e-4 * float(pre.detach().abs().max())
+    pre.backward(gy.double() * mask)
+    assert_close(y.cpu().numpy(), torch.relu(pre).detach().numpy(), 1e-4, "y")
+    _check_grads([("dx", dx, xr.grad), ("dw", dw, wr.grad), ("db", db, br.grad)])
+
+    saved = dict(IF._WG_STREAMS)
+    try:
+        IF.route_weight_gradients(torch.cuda.current_stream(), torch.cuda.Stream())
+        routed = run()
+    finally:
+        IF._WG_STREAMS.clear()
+        IF._WG_STREAMS.update(saved)
+    for name, a, r in zip(("y", "dx", "dw", "db"), (y, dx, dw, db), routed):
+        assert torch.equal(a, r), name
+
+
 @pytest.mark.parametrize("C,H,W,inverse", [(192, 16, 16, False), (192, 8, 5, True), (3, 4, 5, False), (64, 7, 7, False)])
 def test_gdn_fwd_bwd(C, H, W, inverse):
     from image_compression_amd.modelling.layers import GDN
