@@ -216,6 +216,13 @@ SIGNATURES = {
     "ic_ckbd_count": (c_ll, [c_int, c_int, c_int]),
     "ic_ckbd_gather": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
     "ic_ckbd_scatter": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    # gain units: gain vectors from the level tables, the scaling of a latent by them (additive to ic_version 4)
+    "ic_gain_vector": (c_int, [c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
+    "ic_gain_vector_bwd": (c_int, [c_void, c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
+    "ic_channel_scale": (c_int, [c_void, c_void, c_ll, c_ll, c_int, c_int, c_void, c_void]),
+    "ic_channel_scale_bwd_ws": (c_size, [c_ll, c_ll, c_int, c_int]),
+    "ic_channel_scale_bwd": (c_int, [c_void, c_void, c_void, c_ll, c_ll, c_int, c_int, c_void, c_void, c_void, c_size,
+                                     c_void]),
 }
 
 _lib = None
@@ -237,6 +244,7 @@ codec_ops = _namespace("imgcomp_codec", "the entropy coder's ops")
 stream_ops = _namespace("imgcomp_stream", "the segmented coder and the image borders of the per-image streams")
 mean_ops = _namespace("imgcomp_mean", "the mean-scale hyperprior's symbolizers, quantiser and reconstruction")
 ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, parameters and halves")
+gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel scaling")
 
 
 def ops():

@@ -93,6 +93,27 @@ the symbols of its positions in ascending (n, i, j, c) order, chunks cut from th
     chunk lengths of z (u32 each), of the anchors, of the non-anchors, payload of z, of the anchors, of the non-anchors.
 H and W are multiples of 64, so each half holds half of y's symbols.  The three containers do not read one another:
 every parser raises ValueError on another's magic.
+
+Gained containers (little endian): `GainedMeanScaleCompressor2018`, one network for a ladder of rates
+------------------------------------------------------------------------------------------------------
+The model carries four level tables t (S, C) -- gains of y and of z and their inverses -- and codes at a quality q
+in [0, S-1] held as float32.  The gain-vector rule, per table and channel c:
+    s = min(int(floorf(q)), S - 2),  f = q - s,
+    a = fadd(fmul(1 - f, t[s][c]), fmul(f, t[s+1][c]))      (float32, each operation rounded once, none contracted)
+    g[c] = 1.0f if a == 0 else expf(a)
+so an integer q gives exp(t[q]), the values between interpolate geometrically, and zero tables give gains of
+exactly 1.0.  With (g_y, g_y', g_z, g_z') the four vectors at q, every product one float32 multiplication per
+element: the symbols of z are rint(z * g_z); h_s reads z_hat = rint(z * g_z) * g_z'; the symbols of y are
+rint(y * g_y - mu); the reconstruction handed to g_s is (q_y + mu) * g_y'.  Tables, rows, chunks and payloads are
+those of the mean-scale streams (conditional kind 2 or 3).  Both sides compute the gain vectors on the device, by
+the same kernel (csrc/gain.hip), from the float32 quality the stream stores: the decoder never takes it from the
+model.
+    "ICRG" (batch):     the "ICRA" header with this magic, format version 1, then u32 S, f32 quality,
+                        then the chunk lengths and payloads as in "ICRA";
+    "ICRQ" (per image): the "ICRP" header with this magic, format version 1, then u32 S, f32 quality (this image's:
+                        the images of a call may differ), then the chunk lengths and payloads as in "ICRP".
+S >= 2 and a finite quality in [0, S-1], or the parser raises ValueError; a model with another S refuses the stream.
+The five containers do not read one another: every parser raises ValueError on another's magic.
 """
 import math
 import struct
@@ -121,6 +142,12 @@ _IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II")   # the ICRA header's fields,
 CKBD_MAGIC = b"ICRC"
 CKBD_FORMAT_VERSION = 1
 _CKBD_HEAD = struct.Struct(_FIELDS + "III")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
+
+GAINED_MAGIC = b"ICRG"
+GAINED_IMAGE_MAGIC = b"ICRQ"
+GAINED_FORMAT_VERSION = 1
+_GAINED_HEAD = struct.Struct(_FIELDS + "II" + "If")               # the ICRA header, then the gain levels and the quality
+_GAINED_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II" + "If")  # the ICRP header, then the same two
 
 
 @dataclass
@@ -162,6 +189,21 @@ class ImageHeader(Header):
     """Header of the per-image container: N = 1, H x W the padded size, height x width the image's."""
     height: int
     width: int
+
+
+@dataclass
+class GainedHeader(Header):
+    """Header of the gained batch container: the model's number of gain levels S and the quality the batch was
+    coded at, a float32 value in [0, S-1]."""
+    levels: int
+    quality: float
+
+
+@dataclass
+class GainedImageHeader(ImageHeader):
+    """Header of the gained per-image container: ImageHeader, then the levels and this image's quality."""
+    levels: int
+    quality: float
 
 
 def padded_size(h, w):
@@ -381,6 +423,62 @@ def parse_checkerboard(data, abi, compute_dtype):
     launched here."""
     return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, CKBD_FORMAT_VERSION, Header,
                   _check_checkerboard_header, _HALVES, _half_symbols, " (y in two equal halves)")
+
+
+# ---- gained containers "ICRG" (batch) and "ICRQ" (per image): the mean-scale streams of a model with gain units
+def _check_gain(h):
+    if h.levels < 2:
+        raise ValueError(f"codec: {h.levels} gain levels (at least 2)")
+    if not (math.isfinite(h.quality) and 0.0 <= h.quality <= h.levels - 1):
+        raise ValueError(f"codec: quality {h.quality} is outside [0, {h.levels - 1}]")
+    if h.quality != float(np.float32(h.quality)):
+        raise ValueError(f"codec: quality {h.quality!r} is not a float32 value")
+
+
+def _check_gained_header(h):
+    _check_header(h)
+    _check_gain(h)
+
+
+def _check_gained_image_header(h):
+    _check_image_header(h)
+    _check_gain(h)
+
+
+def gained_fixed_bytes(h):
+    """`fixed_bytes` of a gained batch container."""
+    return _fixed_bytes(_GAINED_HEAD, h)
+
+
+def gained_image_fixed_bytes(h):
+    """`fixed_bytes` of a gained per-image container."""
+    return _fixed_bytes(_GAINED_IMAGE_HEAD, h)
+
+
+def pack_gained(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object from a GainedHeader, the two chunk-length tables and the two payloads."""
+    return _pack(_GAINED_HEAD, GAINED_MAGIC, GAINED_FORMAT_VERSION, _check_gained_header, h, (lens_z, lens_y),
+                 (payload_z, payload_y), (h.levels, h.quality))
+
+
+def parse_gained(data, abi, compute_dtype):
+    """(GainedHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_gained`: the checks of
+    `parse`, and those of the levels and the quality.  Nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _GAINED_HEAD, GAINED_MAGIC, GAINED_FORMAT_VERSION, GainedHeader,
+                  _check_gained_header)
+
+
+def pack_gained_image(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object for one image from its GainedImageHeader, chunk-length tables and payloads."""
+    return _pack(_GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION, _check_gained_image_header, h,
+                 (lens_z, lens_y), (payload_z, payload_y), (h.height, h.width, h.levels, h.quality))
+
+
+def parse_gained_image(data, abi, compute_dtype):
+    """(GainedImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_gained_image`: the
+    checks of `parse_image`, and those of the levels and the quality.  Nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION,
+                  GainedImageHeader, _check_gained_image_header)
 
 
 def split_packed_seg(packed, nseg, seg_len, R):

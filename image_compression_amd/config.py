@@ -75,6 +75,8 @@ _DEFAULTS = {
                  "SSIM": {"MAX_VAL": 255., "FILTER_SIZE": 11, "FILTER_SIGMA": 1.5, "K1": 0.01, "K2": 0.03,
                           "LOG_SCALE": False, "EPS": 1e-5},
                  "MS_SSIM_WEIGHTS": [0.0448, 0.2856, 0.3001, 0.2363, 0.1333]},
+        # GainedMeanScaleCompressor2018: the distortion weight of every gain level (the reference's psnr_256 ... psnr_8192)
+        "GAIN": {"LOSS_WEIGHTS": [256., 512., 1024., 2048., 4096., 8192.]},
     },
     "SOLVER": {"USE_ITER": True, "GD_STEPS": 1, "IMS_PER_BATCH": 2, "NUM_CHECKPOINTS": 10,
                "CHECKPOINTER_NAME": "IterCheckpointer", "TRAINER_NAME": "Trainer", "EVALUATOR_NAME": "",

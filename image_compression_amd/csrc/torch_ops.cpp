@@ -1463,6 +1463,116 @@ void ckbd_scatter_meta(const Tensor& half, Tensor& full, int64_t parity) {
               " values) must hold full's ", ckbd_half_numel(full, parity), " values of parity ", parity);
 }
 
+// ---------------------------------------------------------------- gain units (imgcomp_gain)
+// A level table is (S, C); a set of gain vectors (rows, C), one row per quality; a latent is a contiguous
+// (N, *, C) tensor, the channels-last storage the coder flattens, scaled by row 0 (rows == 1) or by row n.
+std::vector<float> check_qualities(c10::ArrayRef<double> q, int64_t S) {
+  TORCH_CHECK_VALUE(S >= 2, "imgcomp_gain: a level table has at least 2 levels, got ", S);
+  TORCH_CHECK_VALUE(!q.empty() && q.size() <= (size_t)INT_MAX, "imgcomp_gain: ", q.size(), " qualities");
+  std::vector<float> out;
+  for (double v : q) {
+    TORCH_CHECK_VALUE(v >= 0.0 && v <= (double)(S - 1), "imgcomp_gain: quality ", v, " is outside [0, ", S - 1, "]");
+    out.push_back((float)v);
+  }
+  return out;
+}
+
+void check_gain_matrix(const Tensor& t, const char* what) {
+  check_operand(t, what);
+  TORCH_CHECK(t.dim() == 2 && t.is_contiguous() && t.size(0) >= 1 && t.size(1) >= 1 && t.numel() <= INT_MAX,
+              "imgcomp_gain: ", what, " must be a non-empty contiguous 2-D tensor, got ", t.sizes());
+}
+
+void check_scale_shapes(const Tensor& x, const Tensor& g) {
+  TORCH_CHECK(x.dim() >= 2 && x.is_contiguous() && x.numel() > 0, "imgcomp_gain: x must be a non-empty contiguous "
+              "(N, *, C) tensor, got ", x.sizes());
+  TORCH_CHECK(g.dim() == 2 && g.is_contiguous() && g.size(1) == x.size(-1) && (g.size(0) == 1 || g.size(0) == x.size(0)),
+              "imgcomp_gain: the gains ", g.sizes(), " must be contiguous (1 or N, C) for x ", x.sizes());
+  TORCH_CHECK(x.size(0) <= 65535 && x.size(-1) <= INT_MAX, "imgcomp_gain: x is too large: ", x.sizes());
+}
+
+void check_scale(const Tensor& x, const Tensor& g) {
+  check_operand(x, "x");
+  check_operand(g, "g");
+  check_scale_shapes(x, g);
+  TORCH_CHECK(x.device() == g.device(), "imgcomp_gain: x and g must be on one device");
+}
+
+Tensor gain_vector(const Tensor& table, c10::ArrayRef<double> q) {
+  check_gain_matrix(table, "table");
+  const std::vector<float> qs = check_qualities(q, table.size(0));
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(table.device());
+  Tensor out = at::empty({(int64_t)qs.size(), table.size(1)}, table.options());
+  check_rc(ic_gain_vector(table.data_ptr<float>(), (int)table.size(0), (int)table.size(1), qs.data(), (int)qs.size(),
+                          out.data_ptr<float>(), stream_of(table)),
+           "gain_vector");
+  return out;
+}
+
+Tensor gain_vector_bwd(const Tensor& g, const Tensor& dout, int64_t S, c10::ArrayRef<double> q) {
+  check_gain_matrix(g, "g");
+  check_gain_matrix(dout, "dout");
+  const std::vector<float> qs = check_qualities(q, S);
+  TORCH_CHECK(g.sizes() == dout.sizes() && g.device() == dout.device() && g.size(0) == (int64_t)qs.size(),
+              "imgcomp_gain: g ", g.sizes(), " and dout ", dout.sizes(), " must be (", qs.size(), ", C) on one device");
+  TORCH_CHECK(S * g.size(1) <= INT_MAX, "imgcomp_gain: the table is too large");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(g.device());
+  Tensor dtable = at::empty({S, g.size(1)}, g.options());
+  check_rc(ic_gain_vector_bwd(g.data_ptr<float>(), dout.data_ptr<float>(), (int)S, (int)g.size(1), qs.data(),
+                              (int)qs.size(), dtable.data_ptr<float>(), stream_of(g)),
+           "gain_vector_bwd");
+  return dtable;
+}
+
+Tensor channel_scale(const Tensor& x, const Tensor& g) {
+  check_scale(x, g);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor out = at::empty_like(x);
+  const int64_t N = x.size(0), C = x.size(-1);
+  check_rc(ic_channel_scale(x.data_ptr<float>(), g.data_ptr<float>(), N, x.numel() / N / C, (int)C, (int)g.size(0),
+                            out.data_ptr<float>(), stream_of(x)),
+           "channel_scale");
+  return out;
+}
+
+std::tuple<Tensor, Tensor> channel_scale_bwd(const Tensor& x, const Tensor& g, const Tensor& dy) {
+  check_scale(x, g);
+  check_operand(dy, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.is_contiguous() && dy.device() == x.device(), "imgcomp_gain: dy ", dy.sizes(),
+              " must be contiguous with the shape ", x.sizes(), " of x, on its device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor dx = at::empty_like(x), dg = at::empty_like(g);
+  const int64_t N = x.size(0), C = x.size(-1), P = x.numel() / N / C;
+  const size_t nb = ic_channel_scale_bwd_ws(N, P, (int)C, (int)g.size(0));
+  Tensor ws = workspace(x, nb);
+  check_rc(ic_channel_scale_bwd(x.data_ptr<float>(), g.data_ptr<float>(), dy.data_ptr<float>(), N, P, (int)C,
+                                (int)g.size(0), dx.data_ptr<float>(), dg.data_ptr<float>(), ws.data_ptr(), nb,
+                                stream_of(x)),
+           "channel_scale_bwd");
+  return {dx, dg};
+}
+
+Tensor gain_vector_meta(const Tensor& table, c10::ArrayRef<double> q) {
+  TORCH_CHECK(table.dim() == 2, "imgcomp_gain: table must be (S, C), got ", table.sizes());
+  check_qualities(q, table.size(0));
+  return at::empty({(int64_t)q.size(), table.size(1)}, table.options());
+}
+Tensor gain_vector_bwd_meta(const Tensor& g, const Tensor& dout, int64_t S, c10::ArrayRef<double> q) {
+  check_qualities(q, S);
+  TORCH_CHECK(g.dim() == 2 && g.sizes() == dout.sizes() && g.size(0) == (int64_t)q.size(), "imgcomp_gain: g ", g.sizes(),
+              " and dout ", dout.sizes(), " must be (", q.size(), ", C)");
+  return at::empty({S, g.size(1)}, g.options());
+}
+Tensor channel_scale_meta(const Tensor& x, const Tensor& g) {
+  check_scale_shapes(x, g);
+  return at::empty_like(x);
+}
+std::tuple<Tensor, Tensor> channel_scale_bwd_meta(const Tensor& x, const Tensor& g, const Tensor& dy) {
+  check_scale_shapes(x, g);
+  TORCH_CHECK(dy.sizes() == x.sizes(), "imgcomp_gain: dy ", dy.sizes(), " must have the shape ", x.sizes(), " of x");
+  return {at::empty_like(x), at::empty_like(g)};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1750,4 +1860,26 @@ TORCH_LIBRARY_IMPL(imgcomp_ckbd, Meta, m) {
   m.impl("params_bwd", ckbd_params_bwd_meta);
   m.impl("gather", ckbd_gather_meta);
   m.impl("scatter", ckbd_scatter_meta);
+}
+
+// The gain units' ops (GainedMeanScaleCompressor2018): additive, in a namespace of their own.
+TORCH_LIBRARY(imgcomp_gain, m) {
+  m.def("gain_vector(Tensor table, float[] q) -> Tensor");
+  m.def("gain_vector_bwd(Tensor g, Tensor dout, int S, float[] q) -> Tensor");
+  m.def("channel_scale(Tensor x, Tensor g) -> Tensor");
+  m.def("channel_scale_bwd(Tensor x, Tensor g, Tensor dy) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_gain, CUDA, m) {
+  m.impl("gain_vector", gain_vector);
+  m.impl("gain_vector_bwd", gain_vector_bwd);
+  m.impl("channel_scale", channel_scale);
+  m.impl("channel_scale_bwd", channel_scale_bwd);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_gain, Meta, m) {
+  m.impl("gain_vector", gain_vector_meta);
+  m.impl("gain_vector_bwd", gain_vector_bwd_meta);
+  m.impl("channel_scale", channel_scale_meta);
+  m.impl("channel_scale_bwd", channel_scale_bwd_meta);
 }

@@ -15,6 +15,8 @@ Kodak evaluator and its metrics, on HIP kernels.
   `graph=True` replays a hipGraph-captured forward per input shape (`GraphForward`);
   `coded=True` also entropy-codes every batch (`model.compress`) and adds `coded_bpp`, the
   bits of the real bitstream per pixel, beside the estimated `bpp`.
+* `rd_sweep(model, batches, qualities)` — one `run_eval` per quality of a model with gain units
+  (GainedMeanScaleCompressor2018): the rate-distortion ladder of one checkpoint.
 """
 import contextlib
 import ctypes
@@ -158,6 +160,26 @@ class GraphForward:
         self.x.copy_(x)
         self.graph.replay()
         return self.x_tilde, self.losses
+
+
+def rd_sweep(model, batches, qualities, coded=True, **evaluator_args):
+    """The rate-distortion ladder of one model with gain units (`set_quality`): one `Evaluator.run_eval` dict per
+    quality over the same batches, with "quality" added; the model's own quality is put back afterwards."""
+    if not hasattr(model, "set_quality"):
+        raise ValueError(f"rd_sweep: {type(model).__name__} has no gain units (set_quality)")
+    if evaluator_args.get("graph"):
+        raise ValueError("rd_sweep: a captured forward replays the quality it was captured at (graph=False only)")
+    batches = list(batches)
+    before = model.quality
+    evaluator = Evaluator(model, coded=coded, **evaluator_args)
+    results = []
+    try:
+        for q in qualities:
+            model.set_quality(q)
+            results.append(dict(evaluator.run_eval(batches), quality=model.quality))
+    finally:
+        model.set_quality(before)
+    return results
 
 
 class Evaluator:

@@ -899,6 +899,56 @@ def ckbd_params(mu_h, sigma_h, a, b):
     return CkbdParamsFn.apply(mu_h, sigma_h, a, b)
 
 
+# ============================================================== gain units
+class GainVectorFn(Function):
+    """(len(q), C) gain vectors of the level table (S, C) at the qualities q (a tuple of floats in [0, S-1]): the
+    gain-vector rule of codec.py (torch.ops.imgcomp_gain.gain_vector / gain_vector_bwd)."""
+
+    @staticmethod
+    def forward(ctx, table, q):
+        _lib.require_device(table)
+        q = [float(v) for v in q]
+        g = _lib.gain_ops().gain_vector(table.contiguous(), q)
+        ctx.save_for_backward(g)
+        ctx.q, ctx.levels = q, int(table.shape[0])
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        g, = ctx.saved_tensors
+        return _lib.gain_ops().gain_vector_bwd(g, dg.contiguous(), ctx.levels, ctx.q), None
+
+
+class ChannelScaleFn(Function):
+    """x (N, C, *) times the gains g (1 or N, C), row 0 for every image or row n for image n: one fp32
+    multiplication per element (torch.ops.imgcomp_gain.channel_scale / channel_scale_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, g):
+        _lib.require_device(x, g)
+        if x.dim() < 2 or g.dim() != 2 or g.shape[1] != x.shape[1] or g.shape[0] not in (1, x.shape[0]):
+            raise ValueError(f"the gains {tuple(g.shape)} must be (1 or N, C) for a tensor of shape {tuple(x.shape)}")
+        xl, g = _to_last(x), g.contiguous()
+        ctx.save_for_backward(xl, g)
+        return _from_last(_lib.gain_ops().channel_scale(xl, g))
+
+    @staticmethod
+    def backward(ctx, dy):
+        xl, g = ctx.saved_tensors
+        dx, dg = _lib.gain_ops().channel_scale_bwd(xl, g, _to_last(dy))
+        return _from_last(dx), dg
+
+
+def gain_vector(table, q):
+    """The gain vectors (len(q), C) of a level table at the qualities q (GainVectorFn)."""
+    return GainVectorFn.apply(table, tuple(q))
+
+
+def channel_scale(x, g):
+    """x (N, C, *) scaled per channel by the gains g (1 or N, C) (ChannelScaleFn)."""
+    return ChannelScaleFn.apply(x, g)
+
+
 class SqDiffFn(Function):
     """(a - b)^2 elementwise: nn.MSELoss(reduction='none')."""
 

@@ -180,11 +180,11 @@ class Compressor2018(nn.Module):
             y_ce = _StreamEdge.apply(y_ce, side)
         else:
             # the serial step of every model, its differences in _hyper_input, _prior and _forward_y
-            z = self.prior_analysis(self._hyper_input(y))
+            z = self._hyper_gain(self.prior_analysis(self._hyper_input(y)))
             z_tilde, _z_probs, z_ce = self.entropy_model(z)
-            y_tilde, y_probs = self._forward_y(y, *self._prior(z_tilde))
+            y_tilde, y_probs = self._forward_y(self._latent_gain(y), *self._prior(self._hyper_ungain(z_tilde)))
             y_ce = self.conditional_model._ce_loss(y_probs)
-            x_tilde = self._reconstruct(y_tilde)
+            x_tilde = self._reconstruct(self._latent_ungain(y_tilde))
             dist = self.distortion_loss(x, x_tilde)
         return x_tilde.detach(), self._losses(z_ce, y_ce, dist, num_pixels)
 
@@ -222,10 +222,32 @@ class Compressor2018(nn.Module):
     # Where a model with another hyperprior or another way of coding y differs (MeanScaleCompressor2018,
     # CheckerboardCompressor2018): what h_a reads (_hyper_input), what h_s gives (_prior), the conditional-kind byte that
     # says so in the container (_stream_kind), how the forward quantises and scores y (_forward_y, above), how y becomes
-    # streams and comes back (_encode_y / _decode_y), and the container of a batch with the checks in front of it
-    # (_pack / _parse, _codable_batch).
+    # streams and comes back (_encode_y / _decode_y), and the containers with the checks in front of them
+    # (_pack / _parse, _pack_image / _parse_image, _codable_batch).  A model that rescales its latents around the
+    # quantisers (GainedMeanScaleCompressor2018) overrides the four gain hooks, identities here, and learns what the
+    # streams it is about to decode say about that in _begin_decode.
     def _hyper_input(self, y):
         return AbsFn.apply(y)
+
+    def _hyper_gain(self, z):
+        """z = h_a(.) as the factorized model quantises and codes it."""
+        return z
+
+    def _hyper_ungain(self, z_hat):
+        """What h_s reads, from the hyper-latent as quantised (every image of the batch by its own rule)."""
+        return z_hat
+
+    def _latent_gain(self, y):
+        """y as the conditional model quantises and codes it."""
+        return y
+
+    def _latent_ungain(self, y_hat):
+        """What g_s reads, from the latent as quantised."""
+        return y_hat
+
+    def _begin_decode(self, headers):
+        """The parsed, checked headers of the streams the next launches decode (one of a batch, or one per image),
+        in front of `_prior`."""
 
     def _prior(self, z_hat):
         """(sigma, mean) from the hyper-latent's integers; mean None: y is coded about 0."""
@@ -247,6 +269,7 @@ class Compressor2018(nn.Module):
         return self.conditional_model.decompress(py, sigma, ly, h.kmax_y, h.R, mean=mean)
 
     _pack, _parse = staticmethod(_codec.pack), staticmethod(_codec.parse)
+    _pack_image, _parse_image = staticmethod(_codec.pack_image), staticmethod(_codec.parse_image)
 
     def _codable_batch(self):
         self._codable()
@@ -270,13 +293,14 @@ class Compressor2018(nn.Module):
         """(y, z, symbols of z, kmax_z, `_prior`): g_a, h_a, and sigma (and the mean) from the integers the decoder
         will hold, in the layout it will hold them in; `each`: one image at a time, as that decoder computes them."""
         y = self.analysis_transform(x)
-        z = self.prior_analysis(self._hyper_input(y))
+        z = self._hyper_gain(self.prior_analysis(self._hyper_input(y)))
         z_sym, kz = self._symbols(z, each=each)
-        z_hat = symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape))
+        z_hat = self._hyper_ungain(symbols_as_tensor(z_sym.to(torch.float32), tuple(z.shape)))
         return y, z, z_sym, kz, (self._prior_each if each else self._prior)(z_hat)
 
-    def _header(self, N, H, W, y, z, steps_per_chunk, kz, ky, size=None):
-        """The Header of a batch's stream, or with `size` = (h, w) the ImageHeader of one image's."""
+    def _header(self, N, H, W, y, z, steps_per_chunk, kz, ky, size=None, image=0):
+        """The Header of a batch's stream, or with `size` = (h, w) the ImageHeader of the stream of image `image` of
+        the call."""
         cm = self.conditional_model
         abi, dtype = self._build_id()
         h = (_codec.Header if size is None else _codec.ImageHeader)(
@@ -305,7 +329,7 @@ class Compressor2018(nn.Module):
         N, _, H, W = x.shape
         y, z, z_sym, kz, prior = self._analyse(x)
         pz, lz = self.entropy_model.encode_symbols(z_sym, kz, steps_per_chunk)
-        ky, streams = self._encode_y(y, prior, steps_per_chunk)
+        ky, streams = self._encode_y(self._latent_gain(y), prior, steps_per_chunk)
         h = self._header(N, H, W, y, z, steps_per_chunk, kz, ky)
         return self._pack(h, lz, *(l for _, l in streams), pz, *(p for p, _ in streams))
 
@@ -317,12 +341,13 @@ class Compressor2018(nn.Module):
         h, *rest = self._parse(data, *self._build_id())
         lens, payloads = rest[:len(rest) // 2], rest[len(rest) // 2:]
         self._check_stream(h, "decompress")
+        self._begin_decode([h])
         z_hat = self.entropy_model.decompress(payloads[0], h.z_shape, lens[0], h.kmax_z, h.R)
-        prior = self._prior(z_hat)
+        prior = self._prior(self._hyper_ungain(z_hat))
         if any(t is not None and tuple(t.shape) != h.y_shape for t in prior):
             raise ValueError(f"decompress: the model's sigma {tuple(prior[0].shape)} is not the stream's latent shape "
                              f"{h.y_shape}")
-        return self._reconstruct(self._decode_y(h, list(zip(payloads[1:], lens[1:])), prior))
+        return self._reconstruct(self._latent_ungain(self._decode_y(h, list(zip(payloads[1:], lens[1:])), prior)))
 
     # ---- per-image streams: any image size, every image its own self-contained stream (container
     # "ICRP", codec.py).  The one rule that makes stream n decodable alone: h_s runs one image at a
@@ -353,11 +378,11 @@ class Compressor2018(nn.Module):
             _lib.require_device(x)
             x = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
         y, z, z_sym, kz, (sigma, mean) = self._analyse(x, each=True)
-        y_sym, ky = self._symbols(y, mean, each=True)
+        y_sym, ky = self._symbols(self._latent_gain(y), mean, each=True)
         sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
         sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), steps_per_chunk, mean=mean)
-        return [_codec.pack_image(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w)),
-                                  sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
+        return [self._pack_image(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w), n),
+                                 sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
 
     @torch.no_grad()
     def decompress_each(self, streams):
@@ -366,7 +391,7 @@ class Compressor2018(nn.Module):
         size and chunk size are decoded by the same launches and pass g_s as one batch."""
         self._codable_each()
         em, cm = self.entropy_model, self.conditional_model
-        parsed = [_codec.parse_image(d, *self._build_id()) for d in streams]   # everything is validated before any launch
+        parsed = [self._parse_image(d, *self._build_id()) for d in streams]   # everything is validated before any launch
         groups = {}
         for m, (h, *_rest) in enumerate(parsed):
             self._check_stream(h, "decompress_each", f"stream {m}")
@@ -374,14 +399,15 @@ class Compressor2018(nn.Module):
         out = [None] * len(parsed)
         for (H, W, _cy, R), idx in groups.items():
             hs = [parsed[m][0] for m in idx]
+            self._begin_decode(hs)
             z_hat = em.decompress_seg([parsed[m][3] for m in idx], hs[0].z_shape, [parsed[m][1] for m in idx],
                                       [h.kmax_z for h in hs], R)
-            sigma, mean = self._prior_each(z_hat)
+            sigma, mean = self._prior_each(self._hyper_ungain(z_hat))
             if tuple(sigma.shape[1:]) != hs[0].y_shape[1:]:
                 raise ValueError(f"decompress_each: the model's sigma {tuple(sigma.shape)} is not the streams' latent "
                                  f"shape {hs[0].y_shape}")
-            y_hat = cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
-                                      [h.kmax_y for h in hs], R, mean=mean)
+            y_hat = self._latent_ungain(cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
+                                                          [h.kmax_y for h in hs], R, mean=mean))
             sizes = {(h.height, h.width) for h in hs}
             if sizes == {(H, W)}:
                 x_hat = self._reconstruct(y_hat).contiguous()

@@ -35,6 +35,10 @@ class TrainStep:
     def __init__(self, model, example_x, graph=True, warmup=3, flat=None):
         if not example_x.is_cuda:
             raise RuntimeError("TrainStep needs a ROCm device tensor")
+        # a model whose step changes on the host from call to call says so (`graph_refusal`): a replay would not
+        refusal = getattr(getattr(model, "module", model), "graph_refusal", None)
+        if graph and refusal:
+            raise RuntimeError(f"TrainStep(graph=True): {refusal}")
         self.model = model
         self.params = [p for p in model.parameters() if p.requires_grad]
         dev = example_x.device

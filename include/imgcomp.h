@@ -586,6 +586,29 @@ int ic_ckbd_gather(const void* src, int elem_bytes, int N, int H, int W, int C, 
 /* the inverse for floats: writes the packed half to its positions of `full`, the other parity untouched */
 int ic_ckbd_scatter(const float* half, int N, int H, int W, int C, int parity, float* full, void* stream);
 
+/* ---- gain units (additive to version 4; GainedMeanScaleCompressor2018).  The gain-vector rule: for a table t
+ *      (S, C), S >= 2, and a quality q in [0, S-1] held as fp32: s = min((int)floorf(q), S-2), f = q - s,
+ *      a = (1-f) t[s][c] + f t[s+1][c] with both products and the sum rounded once each, g[c] = 1.0f where a == 0
+ *      and expf(a) elsewhere.  `q` is a host array.  IC_ERR_ARG before any launch for a null pointer, S < 2, C or
+ *      nq < 1, or a quality that is NaN or outside [0, S-1].  None of them allocates or waits for its stream. ---- */
+/* out[k][c] = the gain of channel c at quality q[k]: (nq, C) */
+int ic_gain_vector(const float* table, int S, int C, const float* q, int nq, float* out, void* stream);
+/* dtable (S, C) from g = ic_gain_vector's output and dout, both (nq, C): one thread per (s, c) sums over k in
+ * ascending order */
+int ic_gain_vector_bwd(const float* g, const float* dout, int S, int C, const float* q, int nq, float* dtable,
+                       void* stream);
+/* x, out: dense (N, P, C) storage, P positions per image, channel fastest; g: (g_rows, C) with g_rows 1 (one gain
+ * for every image) or N (image n takes row n); 1 <= N <= 65535.  out[n,p,c] = x[n,p,c] * g[g_rows == 1 ? 0 : n][c],
+ * one fp32 multiplication */
+int ic_channel_scale(const float* x, const float* g, long long N, long long P, int C, int g_rows, float* out,
+                     void* stream);
+/* dx = dy * g (the forward's multiplication) and dg[row][c] = the sum of dy x over the positions (and the images,
+ * when the row is shared): partial sums per block of positions in `ws`, then one thread per (row, c) over them in
+ * ascending order -- no atomics, bitwise the same from run to run.  The query returns 0 for a shape the call refuses */
+size_t ic_channel_scale_bwd_ws(long long N, long long P, int C, int g_rows);
+int ic_channel_scale_bwd(const float* x, const float* g, const float* dy, long long N, long long P, int C, int g_rows,
+                         float* dx, float* dg, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

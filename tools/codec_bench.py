@@ -17,6 +17,13 @@ no per-image streams) the first mode reports the forward, compress and decompres
 and compress_each / decompress_each at 1 and N images of --height x --width (ms per image, best of --reps), the
 mean-scale model's elementwise ops beside their scale-only counterparts by device events, and the coded bytes of both.
 
+--arch GainedMeanScaleCompressor2018 [--quality q] codes at quality q (default: the model's, its top level).
+
+--gained N times MeanScaleCompressor2018 and GainedMeanScaleCompressor2018 alternately in one process: the eval
+forward, compress and decompress at 1 x --height x --width (seed weights and zero tables: both code the same
+symbols), the gain kernels beside ic_center_round by device events on the y of N images, one eager training step
+of both at 32 x 256 x 256, and the coded bytes at every integer level of a ladder of gains on --scale'd weights.
+
 --each N measures per-image streams instead: N images of --height x --width coded (a) by the loop of
 compress(x[n:n+1]) / decompress and (b) by compress_each / decompress_each, timed alternately in one process
 (best of --reps wall times, device synchronised inside the timed region), then (b) alone on N images of
@@ -172,13 +179,23 @@ def main():
     ap.add_argument("--arch", default="Compressor2018", help="the registered model to measure (META_ARCHITECTURE)")
     ap.add_argument("--compare", type=int, default=0, metavar="N",
                     help="Compressor2018 and MeanScaleCompressor2018 alternately, at 1 and N images")
+    ap.add_argument("--quality", type=float, default=None, help="the quality a model with gain units codes at")
+    ap.add_argument("--gained", type=int, default=0, metavar="N",
+                    help="MeanScaleCompressor2018 and GainedMeanScaleCompressor2018 alternately; kernels on the y of N images")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
     if args.compare:
         _emit(compare_bench(args), args.out)
         return
+    if args.gained:
+        _emit(gained_bench(args), args.out)
+        return
     model, cfg = _build(args.arch, args.scale)
+    if args.quality is not None:
+        if not hasattr(model, "set_quality"):
+            ap.error(f"--quality: {args.arch} has no gain units")
+        model.set_quality(args.quality)
     tag = lambda out: out if args.arch == "Compressor2018" else dict(out, arch=args.arch)
     if args.each:
         _emit(tag(each_bench(args, model, cfg)), args.out)
@@ -206,6 +223,7 @@ def main():
                        "decompress_ms": round(t_d, 3), "bytes": len(data),
                        "coded_bpp": round(8 * len(data) / (args.height * args.width), 5),
                        "container": data[:4].decode(), "decompress_equals_forward": same, "weight_scale": args.scale,
+                       **({"quality": model.quality} if hasattr(model, "set_quality") else {}),
                        "reps": args.reps, "compute_dtype": cfg.MODEL.COMPUTE_DTYPE}), args.out)
             return
         # the coder's ops alone, on this image's latents
@@ -322,6 +340,96 @@ def compare_bench(args):
         }.items()}
         out["elementwise_ops_values"] = y_l.numel()
         out["elementwise_ops_images"] = N
+    return out
+
+
+def gained_bench(args):
+    """--gained N: the mean-scale model and the model with gain units, one repetition of each at a time."""
+    from image_compression_amd import _lib, codec
+    from image_compression_amd import functional as F
+    from image_compression_amd.step import TrainStep
+    archs = ("MeanScaleCompressor2018", "GainedMeanScaleCompressor2018")
+    GAINED = archs[1]
+    models = {a: _build(a, 1.0)[0] for a in archs}      # seed weights, zero tables: the same symbols
+    H, W, reps, N = args.height, args.width, args.reps, args.gained
+    g = torch.Generator(device="cuda").manual_seed(5)
+    out = {"metric": f"mean-scale codec with and without gain units at 3 x {H} x {W}, weight cache, best of {reps} "
+                     "alternating reps", "unit": "ms", "reps": reps,
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0)"}
+    x = torch.rand(1, 3, H, W, device="cuda", generator=g)
+    with torch.no_grad(), F.weight_cache():
+        data = {}
+        for a, m in models.items():
+            for _ in range(2):                               # warm-up of every candidate
+                data[a] = m.compress(x)
+                same = bool(torch.equal(m.decompress(data[a]), m(x)[0]))
+            out[f"{a}_decompress_equals_forward"] = same
+            out[f"{a}_bytes"] = len(data[a])
+        out["same_payload"] = data[archs[0]][codec._HEAD.size:] == data[GAINED][codec._GAINED_HEAD.size:]
+        fns = {"forward": lambda m, a: m(x), "compress": lambda m, a: m.compress(x),
+               "decompress": lambda m, a: m.decompress(data[a])}
+        t = {(k, a): [] for k in fns for a in archs}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                for a, m in models.items():
+                    t[k, a].append(_wall(lambda: fn(m, a), 1))
+        for (k, a), v in t.items():
+            out[f"{a}_{k}_ms"] = round(min(v), 4)
+            out[f"{a}_{k}_all_ms"] = [round(u, 3) for u in v]
+        # the gain kernels beside ic_center_round, by device events on the y of N images; 20 calls between the events
+        m = models[GAINED]
+        gops, mops = _lib.gain_ops(), _lib.mean_ops()
+        xn = torch.rand(N, 3, H, W, device="cuda", generator=g)
+        y = m.analysis_transform(xn)
+        _, mu = m._prior(torch.round(m.prior_analysis(y)))
+        y_l, m_l = y.movedim(1, -1).contiguous(), mu.movedim(1, -1).contiguous()
+        dy = torch.rand_like(y_l)
+        gv = gops.gain_vector(m.gain.log_y, [2.5])
+        gn = gops.gain_vector(m.gain.log_y, [2.5] * N)
+        calls = 20
+        per = lambda fn: _events(lambda: [fn() for _ in range(calls)], reps) / calls
+        n = y_l.numel()
+        kern = {   # name: (ms per call, bytes the kernel must move)
+            "center_round": (per(lambda: mops.center_round(y_l, m_l)), 16 * n),
+            "channel_scale": (per(lambda: gops.channel_scale(y_l, gv)), 8 * n),
+            "channel_scale_per_image": (per(lambda: gops.channel_scale(y_l, gn)), 8 * n),
+            "channel_scale_bwd": (per(lambda: gops.channel_scale_bwd(y_l, gv, dy)), 12 * n),
+            "channel_scale_bwd_per_image": (per(lambda: gops.channel_scale_bwd(y_l, gn, dy)), 12 * n),
+            "gain_vector": (per(lambda: gops.gain_vector(m.gain.log_y, [2.5])), 4 * 3 * y_l.shape[-1]),
+            "gain_vector_bwd": (per(lambda: gops.gain_vector_bwd(gv, gv, m.levels, [2.5])),
+                                4 * (2 + m.levels) * y_l.shape[-1]),
+        }
+        out["kernels_ms_per_call"] = {k: round(v, 5) for k, (v, _) in kern.items()}
+        out["kernels_bytes"] = {k: b for k, (_, b) in kern.items()}
+        out["kernels_gb_per_s"] = {k: round(b / v / 1e6, 1) for k, (v, b) in kern.items()}
+        out["kernels_values"], out["kernels_images"], out["kernels_calls_between_events"] = n, N, calls
+        # coded bytes at every integer level of a ladder of gains, on scaled weights (a table, not a rate result)
+        ms = _build(GAINED, args.scale)[0]
+        for name, sign in (("log_y", 1.0), ("log_inv_y", -1.0), ("log_z", 1.0), ("log_inv_z", -1.0)):
+            getattr(ms.gain, name).copy_(sign * 0.3 * torch.arange(ms.levels, device="cuda").view(-1, 1))
+        ladder = []
+        for s in range(ms.levels):
+            ms.set_quality(s)
+            d = ms.compress(x)
+            h = codec.parse_gained(d, int(_lib.load().ic_version()), "fp32_split")[0]
+            x_hat = ms.decompress(d)
+            ladder.append({"quality": s, "bytes": len(d), "coded_bpp": round(8 * len(d) / (H * W), 5), "kmax_z": h.kmax_z,
+                           "kmax_y": h.kmax_y, "decompress_equals_forward": bool(torch.equal(x_hat, ms(x)[0])),
+                           "mse": float(((x_hat - x) ** 2).mean())})
+        out["ladder_0.3_per_level"], out["ladder_weight_scale"] = ladder, args.scale
+    # one eager training step of both at 32 x 256 x 256
+    xt = torch.rand(32, 3, 256, 256, device="cuda", generator=g)
+    steps = {a: TrainStep(_build(a, 1.0)[0].train(), xt, graph=False) for a in archs}
+    for _ in range(3):
+        for st in steps.values():
+            st()
+    t = {a: [] for a in archs}
+    for _ in range(reps):
+        for a, st in steps.items():
+            t[a].append(_wall(st, 1))
+    for a, v in t.items():
+        out[f"{a}_train_step_32x256x256_ms"] = round(min(v), 3)
+        out[f"{a}_train_step_32x256x256_all_ms"] = [round(u, 3) for u in v]
     return out
 
 
