@@ -216,6 +216,10 @@ SIGNATURES = {
     "ic_ckbd_count": (c_ll, [c_int, c_int, c_int]),
     "ic_ckbd_gather": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
     "ic_ckbd_scatter": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    # the checkerboard context in one batch-invariant launch (additive to ic_version 4)
+    "ic_context_ws": (c_size, [c_int]),
+    "ic_context_fwd": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int,
+                                    c_void, c_void, c_void, c_size, c_int, c_void]),
     # gain units: gain vectors from the level tables, the scaling of a latent by them (additive to ic_version 4)
     "ic_gain_vector": (c_int, [c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
     "ic_gain_vector_bwd": (c_int, [c_void, c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
@@ -245,6 +249,7 @@ stream_ops = _namespace("imgcomp_stream", "the segmented coder and the image bor
 mean_ops = _namespace("imgcomp_mean", "the mean-scale hyperprior's symbolizers, quantiser and reconstruction")
 ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, parameters and halves")
 gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel scaling")
+ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 
 def ops():

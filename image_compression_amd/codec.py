@@ -87,12 +87,28 @@ non-anchor its own (sigma, mu) (modelling/meta_arch/ckbd2021.py `_context`), and
 rint(y - mu), rows index(sigma), reconstruction q + mu.  Each half is a bitstream of its own exactly as specified above:
 the symbols of its positions in ascending (n, i, j, c) order, chunks cut from the half's first symbol.  One K = kmax_y
 (the largest |symbol| of both halves) and so one table set serve both.
-    magic "ICRC", u16 format version (1), then the fields of the "ICRA" header from the arithmetic tag to
+    magic "ICRC", u16 format version (1 or 2), then the fields of the "ICRA" header from the arithmetic tag to
     u64 symbols of y (the conditional kind is 2 or 3: 0 and 1 are rejected),
     u32 chunks of z, u32 chunks of the anchors of y, u32 chunks of the non-anchors of y,
     chunk lengths of z (u32 each), of the anchors, of the non-anchors, payload of z, of the anchors, of the non-anchors.
 H and W are multiples of 64, so each half holds half of y's symbols.  The three containers do not read one another:
 every parser raises ValueError on another's magic.
+The format version names the arithmetic that gave the non-anchors their (sigma, mu), which the decoder must repeat bit
+for bit: 1 -- the two context convs through the conv plans, in the model's COMPUTE_DTYPE (MODEL.CONTEXT.KERNEL "conv");
+2 -- the fused context kernel, exact fp32 and independent of the batch (MODEL.CONTEXT.KERNEL "fused",
+csrc/ckbd_context.hip).  The layout is the same; a model reads only the version it writes, and refuses the other by the
+format-version error before any launch.
+
+Per-image checkerboard container (little endian), one image = one bytes object (`compress_each` of a "fused" model)
+--------------------------------------------------------------------------------------------------------------------
+The image is padded as for "ICRP" and its padded form coded as a checkerboard batch of one: h_s on this image alone,
+the context from the fused kernel (whose result for an image does not depend on what else is in the call), K = the
+largest |symbol| of this image's y over both halves, each half's chunks cut from the half's first symbol of this image.
+    magic "ICRK", u16 format version (1), then the fields of the "ICRP" header from the arithmetic tag to
+    u64 symbols of y, with N = 1, H, W the padded size and the conditional kind 2 or 3,
+    u32 chunks of z, u32 chunks of the anchors of y, u32 chunks of the non-anchors of y,
+    u32 image height h, u32 image width w   (as in "ICRP"),
+    chunk lengths of z (u32 each), of the anchors, of the non-anchors, payload of z, of the anchors, of the non-anchors.
 
 Gained containers (little endian): `GainedMeanScaleCompressor2018`, one network for a ladder of rates
 ------------------------------------------------------------------------------------------------------
@@ -113,7 +129,7 @@ model.
     "ICRQ" (per image): the "ICRP" header with this magic, format version 1, then u32 S, f32 quality (this image's:
                         the images of a call may differ), then the chunk lengths and payloads as in "ICRP".
 S >= 2 and a finite quality in [0, S-1], or the parser raises ValueError; a model with another S refuses the stream.
-The five containers do not read one another: every parser raises ValueError on another's magic.
+The six containers do not read one another: every parser raises ValueError on another's magic.
 """
 import math
 import struct
@@ -140,8 +156,12 @@ IMAGE_FORMAT_VERSION = 1
 _IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II")   # the ICRA header's fields, then image height and width
 
 CKBD_MAGIC = b"ICRC"
-CKBD_FORMAT_VERSION = 1
+CKBD_FORMAT_VERSION = 1          # the context from the two convs
+CKBD_FUSED_FORMAT_VERSION = 2    # the context from the fused, batch-invariant kernel
 _CKBD_HEAD = struct.Struct(_FIELDS + "III")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
+CKBD_IMAGE_MAGIC = b"ICRK"
+CKBD_IMAGE_FORMAT_VERSION = 1
+_CKBD_IMAGE_HEAD = struct.Struct(_FIELDS + "III" + "II")   # the ICRC header, then image height and width
 
 GAINED_MAGIC = b"ICRG"
 GAINED_IMAGE_MAGIC = b"ICRQ"
@@ -410,19 +430,51 @@ def checkerboard_fixed_bytes(h):
     return _fixed_bytes(_CKBD_HEAD, h, _half_symbols)
 
 
-def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn):
+def _checkerboard_version(version):
+    if version not in (CKBD_FORMAT_VERSION, CKBD_FUSED_FORMAT_VERSION):
+        raise ValueError(f"codec: no checkerboard format version {version}")
+    return int(version)
+
+
+def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn, version=CKBD_FORMAT_VERSION):
     """One bytes object from the header, the three chunk-length tables and the three payloads (z, the anchors
-    of y, the non-anchors of y)."""
-    return _pack(_CKBD_HEAD, CKBD_MAGIC, CKBD_FORMAT_VERSION, _check_checkerboard_header, h, (lens_z, lens_ya, lens_yn),
-                 (payload_z, payload_ya, payload_yn), (), _HALVES, _half_symbols)
+    of y, the non-anchors of y); `version`: 1 -- the context came from the convs, 2 -- from the fused kernel."""
+    return _pack(_CKBD_HEAD, CKBD_MAGIC, _checkerboard_version(version), _check_checkerboard_header, h,
+                 (lens_z, lens_ya, lens_yn), (payload_z, payload_ya, payload_yn), (), _HALVES, _half_symbols)
 
 
-def parse_checkerboard(data, abi, compute_dtype):
+def parse_checkerboard(data, abi, compute_dtype, version=CKBD_FORMAT_VERSION):
     """(Header, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
-    `pack_checkerboard`, with the checks of `parse`.  Raises ValueError on anything inconsistent; nothing is
-    launched here."""
-    return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, CKBD_FORMAT_VERSION, Header,
+    `pack_checkerboard` with this `version`, with the checks of `parse`.  Raises ValueError on anything
+    inconsistent, the other version included; nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, _checkerboard_version(version), Header,
                   _check_checkerboard_header, _HALVES, _half_symbols, " (y in two equal halves)")
+
+
+# ---- per-image checkerboard container "ICRK": one image of a "fused" checkerboard model
+def _check_checkerboard_image_header(h):
+    _check_image_header(h)
+    _check_checkerboard_header(h)
+
+
+def checkerboard_image_fixed_bytes(h):
+    """`fixed_bytes` of a per-image checkerboard container."""
+    return _fixed_bytes(_CKBD_IMAGE_HEAD, h, _half_symbols)
+
+
+def pack_checkerboard_image(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn):
+    """One bytes object for one image from its ImageHeader, the three chunk-length tables and the three payloads."""
+    return _pack(_CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, CKBD_IMAGE_FORMAT_VERSION, _check_checkerboard_image_header, h,
+                 (lens_z, lens_ya, lens_yn), (payload_z, payload_ya, payload_yn), (h.height, h.width), _HALVES,
+                 _half_symbols)
+
+
+def parse_checkerboard_image(data, abi, compute_dtype):
+    """(ImageHeader, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
+    `pack_checkerboard_image`: the checks of `parse_checkerboard`, and those of the image size.  Nothing is
+    launched here."""
+    return _parse(data, abi, compute_dtype, _CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, CKBD_IMAGE_FORMAT_VERSION, ImageHeader,
+                  _check_checkerboard_image_header, _HALVES, _half_symbols, " (y in two equal halves)")
 
 
 # ---- gained containers "ICRG" (batch) and "ICRQ" (per image): the mean-scale streams of a model with gain units

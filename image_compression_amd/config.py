@@ -77,6 +77,9 @@ _DEFAULTS = {
                  "MS_SSIM_WEIGHTS": [0.0448, 0.2856, 0.3001, 0.2363, 0.1333]},
         # GainedMeanScaleCompressor2018: the distortion weight of every gain level (the reference's psnr_256 ... psnr_8192)
         "GAIN": {"LOSS_WEIGHTS": [256., 512., 1024., 2048., 4096., 8192.]},
+        # CheckerboardCompressor2018, inference paths only: "conv" -- the two context convs through the conv plans;
+        # "fused" -- one batch-invariant kernel (csrc/ckbd_context.hip), which also gives the model per-image streams
+        "CONTEXT": {"KERNEL": "conv"},
     },
     "SOLVER": {"USE_ITER": True, "GD_STEPS": 1, "IMS_PER_BATCH": 2, "NUM_CHECKPOINTS": 10,
                "CHECKPOINTER_NAME": "IterCheckpointer", "TRAINER_NAME": "Trainer", "EVALUATOR_NAME": "",

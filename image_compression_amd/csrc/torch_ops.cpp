@@ -1463,6 +1463,83 @@ void ckbd_scatter_meta(const Tensor& half, Tensor& full, int64_t parity) {
               " values) must hold full's ", ckbd_half_numel(full, parity), " values of parity ", parity);
 }
 
+// ---------------------------------------------------------------- the context in one launch (imgcomp_ctx)
+// y_in, mu_h, sigma_h as imgcomp_ckbd's full tensors; the weights (C, C, 5, 5) and biases (C) as Conv2d holds them.
+void check_ctx_weights(int64_t C, const Tensor& w, const Tensor& b, const char* head, bool device) {
+  if (device) {
+    check_operand(w, head);
+    check_operand(b, head);
+  }
+  TORCH_CHECK(w.dim() == 4 && w.size(0) == C && w.size(1) == C && w.size(2) == 5 && w.size(3) == 5 && w.is_contiguous(),
+              "imgcomp_ctx: the ", head, " weight must be a contiguous (", C, ", ", C, ", 5, 5) tensor, got ", w.sizes());
+  TORCH_CHECK(b.dim() == 1 && b.size(0) == C && b.is_contiguous(), "imgcomp_ctx: the ", head, " bias must be (", C,
+              "), got ", b.sizes());
+}
+
+std::tuple<Tensor, Tensor> ctx_launch(const Tensor& y_in, const Tensor& mu_h, const Tensor& sigma_h, const Tensor& w_mean,
+                                      const Tensor& b_mean, const Tensor& w_scale, const Tensor& b_scale, Tensor* own_ws,
+                                      bool packed) {
+  check_ckbd(y_in, "y_in");
+  check_ckbd_like(y_in, mu_h, "mu_h");
+  check_ckbd_like(y_in, sigma_h, "sigma_h");
+  const int64_t C = y_in.size(3);
+  check_ctx_weights(C, w_mean, b_mean, "mean", true);
+  check_ctx_weights(C, w_scale, b_scale, "scale", true);
+  for (const Tensor* t : {&w_mean, &b_mean, &w_scale, &b_scale})
+    TORCH_CHECK(t->device() == y_in.device(), "imgcomp_ctx: the weights must be on y_in's device");
+  const size_t nb = ic_context_ws((int)std::min<int64_t>(C, INT_MAX));
+  TORCH_CHECK(nb > 0, "imgcomp_ctx: ", C, " channels (1 .. ", IC_CONTEXT_MAXC, ")");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y_in.device());
+  Tensor ws;
+  if (own_ws) {
+    TORCH_CHECK(own_ws->is_cuda() && own_ws->scalar_type() == at::kByte && own_ws->is_contiguous() &&
+                    own_ws->device() == y_in.device(),
+                "imgcomp_ctx: ws must be a contiguous uint8 tensor on y_in's device");
+    if ((size_t)own_ws->numel() < nb) {
+      TORCH_CHECK(!packed, "imgcomp_ctx: packed weights expected in a workspace of ", own_ws->numel(), " bytes, the op needs ",
+                  nb);
+      own_ws->resize_({(int64_t)nb});
+    }
+    ws = *own_ws;
+  } else {
+    ws = workspace(y_in, nb);
+  }
+  Tensor mu = at::empty_like(y_in), sigma = at::empty_like(y_in);
+  check_rc(ic_context_fwd(y_in.data_ptr<float>(), mu_h.data_ptr<float>(), sigma_h.data_ptr<float>(),
+                               w_mean.data_ptr<float>(), b_mean.data_ptr<float>(), w_scale.data_ptr<float>(),
+                               b_scale.data_ptr<float>(), CKBD_DIMS(y_in), mu.data_ptr<float>(), sigma.data_ptr<float>(),
+                               ws.data_ptr(), (size_t)ws.numel(), packed ? 1 : 0, stream_of(y_in)),
+           "context_fwd");
+  return {mu, sigma};
+}
+
+std::tuple<Tensor, Tensor> ctx_context_fwd(const Tensor& y_in, const Tensor& mu_h, const Tensor& sigma_h,
+                                           const Tensor& w_mean, const Tensor& b_mean, const Tensor& w_scale,
+                                           const Tensor& b_scale) {
+  return ctx_launch(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale, nullptr, false);
+}
+
+// the packed weights kept by the caller: written to `ws` (grown when too small), or with `packed` read from it
+std::tuple<Tensor, Tensor> ctx_context_fwd_ws(const Tensor& y_in, const Tensor& mu_h, const Tensor& sigma_h,
+                                              const Tensor& w_mean, const Tensor& b_mean, const Tensor& w_scale,
+                                              const Tensor& b_scale, Tensor& ws, bool packed) {
+  return ctx_launch(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale, &ws, packed);
+}
+
+std::tuple<Tensor, Tensor> ctx_context_fwd_meta(const Tensor& y_in, const Tensor& mu_h, const Tensor& sigma_h,
+                                                const Tensor& w_mean, const Tensor& b_mean, const Tensor& w_scale,
+                                                const Tensor& b_scale) {
+  check_ckbd_meta(y_in, {&mu_h, &sigma_h});
+  check_ctx_weights(y_in.size(3), w_mean, b_mean, "mean", false);
+  check_ctx_weights(y_in.size(3), w_scale, b_scale, "scale", false);
+  return {at::empty_like(y_in), at::empty_like(y_in)};
+}
+std::tuple<Tensor, Tensor> ctx_context_fwd_ws_meta(const Tensor& y_in, const Tensor& mu_h, const Tensor& sigma_h,
+                                                   const Tensor& w_mean, const Tensor& b_mean, const Tensor& w_scale,
+                                                   const Tensor& b_scale, Tensor& ws, bool packed) {
+  return ctx_context_fwd_meta(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale);
+}
+
 // ---------------------------------------------------------------- gain units (imgcomp_gain)
 // A level table is (S, C); a set of gain vectors (rows, C), one row per quality; a latent is a contiguous
 // (N, *, C) tensor, the channels-last storage the coder flattens, scaled by row 0 (rows == 1) or by row n.
@@ -1860,6 +1937,25 @@ TORCH_LIBRARY_IMPL(imgcomp_ckbd, Meta, m) {
   m.impl("params_bwd", ckbd_params_bwd_meta);
   m.impl("gather", ckbd_gather_meta);
   m.impl("scatter", ckbd_scatter_meta);
+}
+
+// The checkerboard context as one batch-invariant kernel (MODEL.CONTEXT.KERNEL "fused"): additive, in a namespace
+// of its own.  Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_ctx, m) {
+  m.def("context_fwd(Tensor y_in, Tensor mu_h, Tensor sigma_h, Tensor w_mean, Tensor b_mean, Tensor w_scale, "
+        "Tensor b_scale) -> (Tensor, Tensor)");
+  m.def("context_fwd_ws(Tensor y_in, Tensor mu_h, Tensor sigma_h, Tensor w_mean, Tensor b_mean, Tensor w_scale, "
+        "Tensor b_scale, Tensor(a!) ws, bool packed) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_ctx, CUDA, m) {
+  m.impl("context_fwd", ctx_context_fwd);
+  m.impl("context_fwd_ws", ctx_context_fwd_ws);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_ctx, Meta, m) {
+  m.impl("context_fwd", ctx_context_fwd_meta);
+  m.impl("context_fwd_ws", ctx_context_fwd_ws_meta);
 }
 
 // The gain units' ops (GainedMeanScaleCompressor2018): additive, in a namespace of their own.

@@ -899,6 +899,33 @@ def ckbd_params(mu_h, sigma_h, a, b):
     return CkbdParamsFn.apply(mu_h, sigma_h, a, b)
 
 
+def ckbd_context(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale):
+    """(mu, sigma) of every position from the hyperprior's (mu_h, sigma_h), the anchors of y_in and the two context
+    convs' weights (C, C, 5, 5) and biases, by the one batch-invariant kernel (torch.ops.imgcomp_ctx.context_fwd,
+    csrc/ckbd_context.hip): `ckbd_params(mu_h, sigma_h, conv(u), conv(v))` of `(u, v) = ckbd_input(y_in, mu_h)`
+    computing the 12 live taps at the non-anchors only, in exact fp32, image n's result independent of the batch.
+    Inference only: no autograd node.  Inside `weight_cache()` the repacked taps are kept per (weights, versions)."""
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale)):
+        raise RuntimeError("ckbd_context has no backward: call it under torch.no_grad() (training runs the context convs)")
+    yl, ml, sl = _ckbd_pair(y_in, mu_h, sigma_h)
+    _lib.require_device(w_mean, b_mean, w_scale, b_scale)
+    ws_ = [t.detach().contiguous() for t in (w_mean, b_mean, w_scale, b_scale)]
+    if _wcache_on(w_mean):
+        # one entry per mean weight; the scale weight it was packed with is part of its validity
+        e, hit = _wcache_get("context", w_mean, (int(w_mean.shape[0]),))
+        other = e.get("other")
+        hit = hit and other is not None and other[0]() is w_scale and other[1] == w_scale._version
+        e["other"] = (weakref.ref(w_scale), w_scale._version)
+        if "ws" not in e:
+            e["ws"] = torch.empty(16, dtype=torch.uint8, device=yl.device)
+        packed = hit and e.get("packed", False)
+        mu, sigma = _lib.ctx_ops().context_fwd_ws(yl, ml, sl, *ws_, e["ws"], bool(packed))
+        e["packed"] = packed or yl.shape[1] * yl.shape[2] > 1   # a 1 x 1 map has no non-anchor: nothing is packed for it
+    else:
+        mu, sigma = _lib.ctx_ops().context_fwd(yl, ml, sl, *ws_)
+    return _from_last(mu), _from_last(sigma)
+
+
 # ============================================================== gain units
 class GainVectorFn(Function):
     """(len(q), C) gain vectors of the level table (S, C) at the qualities q (a tuple of floats in [0, S-1]): the

@@ -192,9 +192,16 @@ class Compressor2018(nn.Module):
         """(y_tilde, p_y) of the forward from y and `_prior`'s (sigma, mean): how y is quantised and scored."""
         return self.conditional_model(y, sigma)
 
-    def _reconstruct(self, y_hat):
-        """g_s and the clamp to [0, 1]."""
-        return LowerBound.apply(UpperBound.apply(self.synthesis_transform(y_hat), 1.), 0.)
+    def _reconstruct(self, y_hat, sizes=None):
+        """g_s and the clamp to [0, 1].  With `sizes`, the (h, w) of every image of the batch: a list of the images
+        (1, 3, h, w), each the top-left corner of its reconstruction (the per-image streams' crop, inference only)."""
+        x = self.synthesis_transform(y_hat)
+        if sizes is None:
+            return LowerBound.apply(UpperBound.apply(x, 1.), 0.)
+        if len(set(sizes)) == 1:
+            x = _lib.stream_ops().crop_clamp(x, *sizes[0])
+            return [x[k:k + 1] for k in range(len(sizes))]
+        return [_lib.stream_ops().crop_clamp(x[k:k + 1], h, w) for k, (h, w) in enumerate(sizes)]
 
     def _losses(self, z_ce, y_ce, dist, num_pixels):
         total_dist = sum(dist.values())
@@ -365,18 +372,24 @@ class Compressor2018(nn.Module):
         sigma, mean = zip(*parts)
         return torch.cat(sigma), (None if mean[0] is None else torch.cat(mean))
 
-    @torch.no_grad()
-    def compress_each(self, x, steps_per_chunk=1024):
-        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> a list of N bytes objects, one stream per image."""
-        self._codable_each()
+    @staticmethod
+    def _pad_each(x):
+        """(x padded at the bottom and the right to multiples of 64 by replicating its edge, (N, h, w, H, W))."""
         if x.dim() != 4 or min(x.shape) < 1:
             raise ValueError(f"compress_each: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
-        em, cm = self.entropy_model, self.conditional_model
         N, _, h, w = x.shape
         H, W = _codec.padded_size(h, w)
         if (H, W) != (h, w):
             _lib.require_device(x)
             x = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
+        return x, (N, h, w, H, W)
+
+    @torch.no_grad()
+    def compress_each(self, x, steps_per_chunk=1024):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> a list of N bytes objects, one stream per image."""
+        self._codable_each()
+        em, cm = self.entropy_model, self.conditional_model
+        x, (N, h, w, H, W) = self._pad_each(x)
         y, z, z_sym, kz, (sigma, mean) = self._analyse(x, each=True)
         y_sym, ky = self._symbols(self._latent_gain(y), mean, each=True)
         sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
@@ -408,17 +421,15 @@ class Compressor2018(nn.Module):
                                  f"shape {hs[0].y_shape}")
             y_hat = self._latent_ungain(cm.decompress_seg([parsed[m][4] for m in idx], sigma, [parsed[m][2] for m in idx],
                                                           [h.kmax_y for h in hs], R, mean=mean))
-            sizes = {(h.height, h.width) for h in hs}
-            if sizes == {(H, W)}:
-                x_hat = self._reconstruct(y_hat).contiguous()
-                imgs = [x_hat[k:k + 1] for k in range(len(idx))]
-            else:
-                x_hat = self.synthesis_transform(y_hat)
-                if len(sizes) == 1:
-                    x_hat = _lib.stream_ops().crop_clamp(x_hat, *next(iter(sizes)))
-                    imgs = [x_hat[k:k + 1] for k in range(len(idx))]
-                else:
-                    imgs = [_lib.stream_ops().crop_clamp(x_hat[k:k + 1], h.height, h.width) for k, h in enumerate(hs)]
-            for m, img in zip(idx, imgs):
+            for m, img in zip(idx, self._reconstruct_each(y_hat, hs)):
                 out[m] = img
         return out
+
+    def _reconstruct_each(self, y_hat, hs):
+        """[x_hat of image k, (1, 3, h_k, w_k)] from the latents of a group of streams that share one padded size, and
+        their headers: g_s on the group as one batch, then each image cropped to its own size and clamped."""
+        sizes = [(h.height, h.width) for h in hs]
+        if set(sizes) == {(hs[0].H, hs[0].W)}:
+            x_hat = self._reconstruct(y_hat).contiguous()
+            return [x_hat[k:k + 1] for k in range(len(hs))]
+        return self._reconstruct(y_hat, sizes)

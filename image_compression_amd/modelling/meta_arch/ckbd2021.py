@@ -23,14 +23,25 @@ their multiply-adds)
 Decodability: the contract of Compressor2018.decompress (same weights, build, COMPUTE_DTYPE, device type and batch
 shape) and nothing more.  The two sides agree bit for bit on the non-anchors' (sigma, mu) because the decoder's
 `add_mean` is `center_round`'s addition, so u and v are identical at the anchors and +0.0 elsewhere on both sides,
-and the convs are deterministic for a given shape, arithmetic and build."""
+and the convs are deterministic for a given shape, arithmetic and build.
+
+MODEL.CONTEXT.KERNEL.  "conv" (the default) is everything above.  "fused" changes how the inference paths -- the eval
+forward, `compress`, `decompress` -- compute `_context`: one kernel (functional.ckbd_context, csrc/ckbd_context.hip)
+that evaluates the 12 live taps at the non-anchors only, in exact fp32 whatever COMPUTE_DTYPE is, and gives image n
+the same bits whatever the batch around it.  The training forward keeps the convs (autograd lives there), the
+parameters and the state dict are the same, so one checkpoint loads under either value.  Because the two routes round
+differently, their batch streams are told apart by the "ICRC" format version (1: convs, 2: fused kernel), and each
+model refuses the other's.  Because the fused context does not depend on the batch, a "fused" model also has
+per-image streams (`compress_each` / `decompress_each`, container "ICRK"): h_s runs image by image as in every
+model, the context once for the whole call."""
 import torch
 import torch.nn as nn
 
 from ... import codec as _codec
 from ...functional import conditional_likelihood
-from ..blocks.entropy_model import (_decode, _encode, add_mean, center_round, ckbd_gather, ckbd_input, ckbd_params,
-                                    ckbd_scatter, symbolize_mean)
+from ...functional import ckbd_context
+from ..blocks.entropy_model import (_decode, _decode_seg, _encode, _encode_seg, add_mean, center_round, ckbd_gather,
+                                    ckbd_input, ckbd_params, ckbd_scatter, symbolize_mean)
 from ..layers import Conv2d
 from .build import META_ARCH_REGISTRY
 from .mshp2018 import MeanScaleCompressor2018
@@ -53,10 +64,18 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         for conv in (self.context_mean, self.context_scale):
             nn.init.zeros_(conv.weight.data)
             nn.init.zeros_(conv.bias.data)
+        # how the inference paths compute `_context`; no parameter or state-dict key depends on it
+        self.context_kernel = cfg.MODEL.get("CONTEXT", {}).get("KERNEL", "conv")
+        if self.context_kernel not in ("conv", "fused"):
+            raise ValueError(f'MODEL.CONTEXT.KERNEL {self.context_kernel!r}: expected "conv" or "fused"')
 
     def _context(self, y_in, sigma_h, mu_h):
         """(sigma, mu) of every position from the hyperprior's (sigma_h, mu_h) and the anchors of y_in; the whole
         dependence on neighbours is here.  y_in's non-anchors are not read."""
+        if self.context_kernel == "fused" and not self.training:
+            cm, cs = self.context_mean, self.context_scale
+            mu, sigma = ckbd_context(y_in, mu_h, sigma_h, cm.weight, cm.bias, cs.weight, cs.bias)
+            return sigma, mu
         u, v = ckbd_input(y_in, mu_h)
         mu, sigma = ckbd_params(mu_h, sigma_h, self.context_mean(u), self.context_scale(v))
         return sigma, mu
@@ -76,8 +95,16 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         r, y_tilde = center_round(y, mu)   # at the anchors mu is mu_h bit for bit: one call serves both halves
         return y_tilde, cm.likelihood(r, sigma)
 
-    # ---- bitstreams: container "ICRC" (codec.py), y as two streams -- the anchors, then the non-anchors
-    _pack, _parse = staticmethod(_codec.pack_checkerboard), staticmethod(_codec.parse_checkerboard)
+    # ---- bitstreams: container "ICRC" (codec.py), y as two streams -- the anchors, then the non-anchors.  The format
+    # version says which route computed the context, so a stream is only ever decoded by the arithmetic that coded it
+    def _format_version(self):
+        return _codec.CKBD_FUSED_FORMAT_VERSION if self.context_kernel == "fused" else _codec.CKBD_FORMAT_VERSION
+
+    def _pack(self, *parts):
+        return _codec.pack_checkerboard(*parts, version=self._format_version())
+
+    def _parse(self, data, abi, compute_dtype):
+        return _codec.parse_checkerboard(data, abi, compute_dtype, version=self._format_version())
 
     def _codable_batch(self):
         self._codable_each()    # BIN == 1, before anything is computed
@@ -109,11 +136,77 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         ckbd_scatter(_decode(pn, ln, half, rows, 0, tables, h.R, dev), flat, h.y_shape, 1)
         return add_mean(flat, mu)
 
-    # Per-image streams need the context convs run one image at a time on both sides, as h_s is (`_prior_each`): not built.
-    def compress_each(self, x, steps_per_chunk=1024):
-        self._codable()
-        raise NotImplementedError("CheckerboardCompressor2018 has no per-image streams (compress_each): use compress")
+    # ---- per-image streams: container "ICRK" (codec.py), "fused" only.  With the convs, a non-anchor's (sigma, mu)
+    # bits depend on the batch shape (the conv plans' kernel instance and split-K do), so a lone decoder could not
+    # reproduce them; the fused context gives image n the same bits in any call, and h_s runs image by image as in
+    # every model (`_prior_each`).
+    def _codable_fused(self, what):
+        if self.context_kernel != "fused":
+            self._codable()
+            raise NotImplementedError(f"CheckerboardCompressor2018 has no per-image streams ({what}): use "
+                                      f"{what[:-len('_each')]} (or build the model with MODEL.CONTEXT.KERNEL \"fused\")")
+        self._codable_each()
 
+    @torch.no_grad()
+    def compress_each(self, x, steps_per_chunk=1024):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> a list of N bytes objects, one "ICRK" stream per image."""
+        self._codable_fused("compress_each")
+        em, cm = self.entropy_model, self.conditional_model
+        x, (N, h, w, H, W) = self._pad_each(x)
+        y, z, z_sym, kz, (sigma_h, mu_h) = self._analyse(x, each=True)
+        sigma, mu = self._eval_params(y, sigma_h, mu_h)      # one launch for the whole call
+        y_sym, ky = self._symbols(y, mu, each=True)          # one K per image, serving both of its halves
+        sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
+        shape, rows, tables_of = tuple(y.shape), cm.scale_rows(sigma), self._tables_of(y.device)
+        # image n's half is contiguous in the gathered buffers: the segments of the segmented coder are the images
+        (sa, sn) = (_encode_seg(ckbd_gather(y_sym, shape, p), N, ckbd_gather(rows, shape, p), 0, tables_of, ky,
+                                steps_per_chunk) for p in (0, 1))
+        return [_codec.pack_checkerboard_image(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w), n),
+                                               sz[n][1], sa[n][1], sn[n][1], sz[n][0], sa[n][0], sn[n][0])
+                for n in range(N)]
+
+    def _tables_of(self, device):
+        """K -> the conditional model's tables, each K built once for the two halves."""
+        built = {}
+
+        def tables_of(K):
+            if K not in built:
+                built[K] = self.conditional_model.tables(K, device)
+            return built[K]
+        return tables_of
+
+    @torch.no_grad()
     def decompress_each(self, streams):
-        self._codable()
-        raise NotImplementedError("CheckerboardCompressor2018 has no per-image streams (decompress_each): use decompress")
+        """A list of M bytes objects from `compress_each` (any sizes, coded in any calls; same weights, build,
+        COMPUTE_DTYPE and device type) -> a list of M tensors (1, 3, h_m, w_m).  Streams that share a padded size and
+        chunk size are decoded by the same launches: all their anchors, one context, all their non-anchors, one g_s."""
+        self._codable_fused("decompress_each")
+        em, cm = self.entropy_model, self.conditional_model
+        parsed = [_codec.parse_checkerboard_image(d, *self._build_id()) for d in streams]   # all validated before any launch
+        groups = {}
+        for m, (h, *_rest) in enumerate(parsed):
+            self._check_stream(h, "decompress_each", f"stream {m}")
+            groups.setdefault((h.H, h.W, h.latent_channels, h.R), []).append(m)
+        out = [None] * len(parsed)
+        for (_H, _W, _cy, R), idx in groups.items():
+            hs = [parsed[m][0] for m in idx]
+            lz, la, ln, pz, pa, pn = ([parsed[m][k] for m in idx] for k in range(1, 7))
+            z_hat = em.decompress_seg(pz, hs[0].z_shape, lz, [h.kmax_z for h in hs], R)
+            sigma_h, mu_h = self._prior_each(z_hat)
+            shape = (len(idx), *hs[0].y_shape[1:])
+            if tuple(sigma_h.shape) != shape:
+                raise ValueError(f"decompress_each: the model's sigma {tuple(sigma_h.shape)} is not the streams' latent "
+                                 f"shape {shape}")
+            dev, half, kys = sigma_h.device, hs[0].nsym_y // 2, [h.kmax_y for h in hs]
+            tables_of = self._tables_of(dev)
+            flat = torch.zeros(len(idx) * hs[0].nsym_y, dtype=torch.float32, device=dev)
+            # pass one: every image's anchors, under the hyperprior's own parameters
+            rows = ckbd_gather(cm.scale_rows(sigma_h), shape, 0)
+            ckbd_scatter(_decode_seg(pa, la, half, rows, 0, tables_of, kys, R, dev), flat, shape, 0)
+            sigma, mu = self._context(add_mean(flat, mu_h), sigma_h, mu_h)
+            # pass two: every image's non-anchors, under the parameters its decoded anchors give them
+            rows = ckbd_gather(cm.scale_rows(sigma), shape, 1)
+            ckbd_scatter(_decode_seg(pn, ln, half, rows, 0, tables_of, kys, R, dev), flat, shape, 1)
+            for m, img in zip(idx, self._reconstruct_each(add_mean(flat, mu), hs)):
+                out[m] = img
+        return out

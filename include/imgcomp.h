@@ -586,6 +586,30 @@ int ic_ckbd_gather(const void* src, int elem_bytes, int N, int H, int W, int C, 
 /* the inverse for floats: writes the packed half to its positions of `full`, the other parity untouched */
 int ic_ckbd_scatter(const float* half, int N, int H, int W, int C, int parity, float* full, void* stream);
 
+/* ---- the checkerboard context in one batch-invariant launch (additive to version 4; csrc/ckbd_context.hip).
+ *      y_in, mu_h, sigma_h, mu, sigma: N x H x W x C as above; w_mean, w_scale: (C, C, 5, 5) and b_mean, b_scale: (C),
+ *      as a Conv2d holds them.  At the anchors mu = mu_h and sigma = sigma_h bit for bit.  At a non-anchor, over the
+ *      12 taps (ky, kx) with (ky-2) + (kx-2) odd in ascending order, a neighbour outside the map contributing 0:
+ *          a[o] = b_mean[o]  + sum_t sum_c w_mean[o,c,ky,kx]  y_in[c, nbr]
+ *          b[o] = b_scale[o] + sum_t sum_c w_scale[o,c,ky,kx] |y_in[c, nbr] - mu_h[c, nbr]|
+ *          mu = mu_h + a,  sigma = sigma_h expf(clamp(b, -4, 4))            (ic_ckbd_params_fwd's rule)
+ *      in exact fp32 products with fp32 accumulation (fp32 MFMA) whatever the model's arithmetic.  The other 13
+ *      taps and the non-anchors of y_in are never read.  Image n's outputs depend on image n's inputs, the
+ *      weights and (H, W, C) only -- bit for bit, whatever N and wherever in the batch the image lies: tiles are
+ *      cut per image, every sum runs in one fixed order, nothing is split by the launch size, no atomics.
+ *      `ws`: 16-byte aligned, at least ic_context_ws(C) bytes; it receives the repacked live taps, and with
+ *      `packed` != 0 it already holds them (from an earlier call with these weights) and is only read.
+ *      IC_ERR_ARG before any launch for a null pointer, a size below 1, C > IC_CONTEXT_MAXC, N H W C past
+ *      2^63 - 1, or an output that shares a buffer with the other output or an input; IC_ERR_WORKSPACE for a short
+ *      workspace.  A 1 x 1 map has no non-anchor: nothing is packed and the launch only copies.  Neither allocates
+ *      or waits for its stream. ---- */
+#define IC_CONTEXT_MAXC 4096
+/* bytes of the packed weights; 0: C outside 1 .. IC_CONTEXT_MAXC */
+size_t ic_context_ws(int C);
+int ic_context_fwd(const float* y_in, const float* mu_h, const float* sigma_h, const float* w_mean,
+                        const float* b_mean, const float* w_scale, const float* b_scale, int N, int H, int W, int C,
+                        float* mu, float* sigma, void* ws, size_t ws_bytes, int packed, void* stream);
+
 /* ---- gain units (additive to version 4; GainedMeanScaleCompressor2018).  The gain-vector rule: for a table t
  *      (S, C), S >= 2, and a quality q in [0, S-1] held as fp32: s = min((int)floorf(q), S-2), f = q - s,
  *      a = (1-f) t[s][c] + f t[s+1][c] with both products and the sum rounded once each, g[c] = 1.0f where a == 0

@@ -24,6 +24,16 @@ forward, compress and decompress at 1 x --height x --width (seed weights and zer
 symbols), the gain kernels beside ic_center_round by device events on the y of N images, one eager training step
 of both at 32 x 256 x 256, and the coded bytes at every integer level of a ladder of gains on --scale'd weights.
 
+--context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
+--each works on it too (its loop arm is then the fused model's own compress / decompress).
+
+--context-compare N times the "conv" and the "fused" checkerboard model (same weights, a nonzero context)
+alternately in one process: the eval forward, compress and decompress of one --height x --width image; the context
+alone by device events on that image's latent (two convs and two elementwise ops against the one kernel); the loop
+of the conv model's compress(x[n:n+1]) / decompress against the fused model's compress_each / decompress_each on N
+images, and the latter on N images of 500 x 750; and the bytes of the "ICRK" streams beside "ICRC" version 2 and
+the mean-scale model's "ICRP" streams of the same images.
+
 --each N measures per-image streams instead: N images of --height x --width coded (a) by the loop of
 compress(x[n:n+1]) / decompress and (b) by compress_each / decompress_each, timed alternately in one process
 (best of --reps wall times, device synchronised inside the timed region), then (b) alone on N images of
@@ -182,16 +192,23 @@ def main():
     ap.add_argument("--quality", type=float, default=None, help="the quality a model with gain units codes at")
     ap.add_argument("--gained", type=int, default=0, metavar="N",
                     help="MeanScaleCompressor2018 and GainedMeanScaleCompressor2018 alternately; kernels on the y of N images")
+    ap.add_argument("--context", choices=("conv", "fused"), default="conv",
+                    help="MODEL.CONTEXT.KERNEL of CheckerboardCompressor2018")
+    ap.add_argument("--context-compare", type=int, default=0, metavar="N", dest="context_compare",
+                    help='the "conv" and the "fused" checkerboard model alternately; per-image streams at N images')
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.context_compare:
+        _emit(context_bench(args), args.out)
+        return
     if args.compare:
         _emit(compare_bench(args), args.out)
         return
     if args.gained:
         _emit(gained_bench(args), args.out)
         return
-    model, cfg = _build(args.arch, args.scale)
+    model, cfg = _build(args.arch, args.scale, args.context)
     if args.quality is not None:
         if not hasattr(model, "set_quality"):
             ap.error(f"--quality: {args.arch} has no gain units")
@@ -271,11 +288,12 @@ def main():
     _emit(tag(out), args.out)
 
 
-def _build(arch, scale):
+def _build(arch, scale, context="conv"):
     from image_compression_amd import get_cfg_defaults, modelling
     cfg = get_cfg_defaults()
     cfg.MODEL.LOSS.REDUCTION = "mean"
     cfg.MODEL.META_ARCHITECTURE = arch
+    cfg.MODEL.CONTEXT.KERNEL = context
     torch.manual_seed(0)
     model = modelling.build_model(cfg).cuda().eval()
     if scale != 1.0:
@@ -340,6 +358,113 @@ def compare_bench(args):
         }.items()}
         out["elementwise_ops_values"] = y_l.numel()
         out["elementwise_ops_images"] = N
+    return out
+
+
+def context_bench(args):
+    """--context-compare N: the checkerboard model with the context convs and with the fused context kernel."""
+    from image_compression_amd import _lib, codec
+    from image_compression_amd import functional as F
+    from image_compression_amd.modelling.blocks.entropy_model import ckbd_input, ckbd_params
+    CK = "CheckerboardCompressor2018"
+    models = {k: _build(CK, args.scale, k)[0] for k in ("conv", "fused")}
+    mean = _build("MeanScaleCompressor2018", args.scale)[0]
+    gw = torch.Generator().manual_seed(1)
+    with torch.no_grad():                                    # one nonzero context, all 25 taps, in both models
+        for name, std in (("context_mean", 0.02), ("context_scale", 0.005)):
+            w = torch.randn(getattr(models["conv"], name).weight.shape, generator=gw) * std
+            b = torch.randn(getattr(models["conv"], name).bias.shape, generator=gw) * std
+            for m in models.values():
+                getattr(m, name).weight.copy_(w)
+                getattr(m, name).bias.copy_(b)
+    H, W, reps, N = args.height, args.width, args.reps, args.context_compare
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x1 = torch.rand(1, 3, H, W, device="cuda", generator=g)
+    xn = torch.rand(N, 3, H, W, device="cuda", generator=g)
+    x_odd = torch.rand(N, 3, 500, 750, device="cuda", generator=g)
+    out = {"metric": f"checkerboard context, convs against the fused kernel, 3 x {H} x {W}, weight cache, best of {reps} "
+                     "alternating reps", "unit": "ms", "reps": reps, "weight_scale": args.scale, "images": N,
+           "compute_dtype": "fp32_split",
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0), "
+                   "seeded normal context weights"}
+    with torch.no_grad(), F.weight_cache():
+        # (a) one image: forward, compress, decompress
+        data = {}
+        for k, m in models.items():
+            for _ in range(2):
+                data[k] = m.compress(x1)
+                same = bool(torch.equal(m.decompress(data[k]), m(x1)[0]))
+            out[f"{k}_decompress_equals_forward"] = same
+            out[f"{k}_bytes_n1"] = len(data[k])
+        fns = {"forward": lambda m, k: m(x1), "compress": lambda m, k: m.compress(x1),
+               "decompress": lambda m, k: m.decompress(data[k])}
+        t = {(f, k): [] for f in fns for k in models}
+        for _ in range(reps):
+            for f, fn in fns.items():
+                for k, m in models.items():
+                    t[f, k].append(_wall(lambda: fn(m, k), 1))
+        for (f, k), v in t.items():
+            out[f"{k}_{f}_ms_n1"] = round(min(v), 4)
+        # the context alone, by device events, on that image's latent and on the N images'; 10 calls between the events
+        calls = 10
+        for tag_, x in (("n1", x1), (f"n{N}", xn)):
+            m = models["fused"]
+            y = m.analysis_transform(x)
+            sigma_h, mu_h = m._prior(torch.round(m.prior_analysis(y)))
+            y_in = torch.round(y - mu_h) + mu_h
+            for k, mk in models.items():
+                mk._context(y_in, sigma_h, mu_h)
+                ms = _events(lambda: [mk._context(y_in, sigma_h, mu_h) for _ in range(calls)], reps) / calls
+                out[f"{k}_context_alone_ms_{tag_}"] = round(ms, 5)
+            (sc, mc), (sf, mf) = (mk._context(y_in, sigma_h, mu_h) for mk in models.values())
+            out[f"context_max_diff_over_max_mu_sigma_{tag_}"] = [float((mc - mf).abs().max() / mc.abs().max()),
+                                                                float((sc - sf).abs().max() / sc.abs().max())]
+            out[f"context_latent_{tag_}"] = list(y.shape)
+        # (b) N images: the conv model's loop of single-image batches against the fused model's per-image streams
+        conv, fused = models["conv"], models["fused"]
+        loop_c = lambda: [conv.compress(xn[n:n + 1]) for n in range(N)]
+        loop_d = lambda: [conv.decompress(d) for d in datas]
+        each_c = lambda: fused.compress_each(xn)
+        each_d = lambda: fused.decompress_each(streams)
+        for _ in range(2):
+            datas, streams, odd = loop_c(), each_c(), fused.compress_each(x_odd)
+            loop_d(), each_d(), fused.decompress_each(odd)
+        # the streams decoded one at a time against all together: the latents are the same bits (tests/test_context_gpu.py),
+        # the images follow g_s, whose low bits depend on the batch it runs in
+        together = each_d()
+        out["decompress_each_alone_max_diff_to_together"] = max(
+            float((fused.decompress_each([s])[0] - t).abs().max()) for s, t in zip(streams, together))
+        t = {"loop_compress": [], "each_compress": [], "loop_decompress": [], "each_decompress": []}
+        for _ in range(reps):
+            t["loop_compress"].append(_wall(loop_c, 1))
+            t["each_compress"].append(_wall(each_c, 1))
+            t["loop_decompress"].append(_wall(loop_d, 1))
+            t["each_decompress"].append(_wall(each_d, 1))
+        best = {k: min(v) for k, v in t.items()}
+        for k, v in best.items():
+            out[f"{k}_ms_per_image"] = round(v / N, 4)
+        out["each_no_slower_than_loop"] = bool(best["each_compress"] <= best["loop_compress"]
+                                               and best["each_decompress"] <= best["loop_decompress"])
+        out["all_reps_ms_per_batch"] = {k: [round(u, 3) for u in v] for k, v in t.items()}
+        out["padded_500x750_each_compress_ms_per_image"] = round(_wall(lambda: fused.compress_each(x_odd), reps) / N, 4)
+        out["padded_500x750_each_decompress_ms_per_image"] = round(_wall(lambda: fused.decompress_each(odd), reps) / N, 4)
+        # (c) bytes: "ICRK" per image against "ICRC" version 2 of single-image batches and the mean-scale "ICRP"
+        abi = int(_lib.load().ic_version())
+        batch1 = [fused.compress(xn[n:n + 1]) for n in range(N)]
+        icrp = mean.compress_each(xn)
+        hk = [codec.parse_checkerboard_image(d, abi, "fp32_split")[0] for d in streams]
+        out["bytes_icrk"], out["bytes_icrc_v2_single_image_batches"] = sum(map(len, streams)), sum(map(len, batch1))
+        out["bytes_icrc_v1_single_image_batches"], out["bytes_mean_scale_icrp"] = sum(map(len, datas)), sum(map(len, icrp))
+        out["bytes_icrk_500x750"] = sum(map(len, odd))
+        # with a zero context the symbols are the mean-scale model's: what is left is the container
+        zero = _build(CK, args.scale, "fused")[0].compress_each(xn)
+        out["bytes_icrk_zero_context"] = sum(map(len, zero))
+        out["icrk_zero_context_minus_icrp_per_image"] = [len(a) - len(b) for a, b in zip(zero, icrp)]
+        out["icrk_minus_icrc_v2_per_image"] = [len(a) - len(b) for a, b in zip(streams, batch1)]
+        out["header_bytes"] = {"ICRK": codec._CKBD_IMAGE_HEAD.size, "ICRC": codec._CKBD_HEAD.size, "ICRP": codec._IMAGE_HEAD.size}
+        out["fixed_bytes_icrk"] = [codec.checkerboard_image_fixed_bytes(h) for h in hk]
+        out["fixed_bytes_mean_scale_icrp"] = [codec.image_fixed_bytes(codec.parse_image(d, abi, "fp32_split")[0]) for d in icrp]
+        out["kmax_y_icrk"] = [h.kmax_y for h in hk]
     return out
 
 
