@@ -227,6 +227,17 @@ SIGNATURES = {
     "ic_channel_scale_bwd_ws": (c_size, [c_ll, c_ll, c_int, c_int]),
     "ic_channel_scale_bwd": (c_int, [c_void, c_void, c_void, c_ll, c_ll, c_int, c_int, c_void, c_void, c_void, c_size,
                                      c_void]),
+    # region-of-interest coding: scaling by a gain row per block, the block-weighted squared error (additive to
+    # ic_version 4)
+    "ic_block_scale": (c_int, [c_void, c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_int, c_void, c_void]),
+    "ic_block_scale_bwd_ws": (c_size, [c_int, c_int, c_int, c_int, c_int]),
+    "ic_block_scale_bwd": (c_int, [c_void, c_void, c_int, c_void, c_void, c_int, c_int, c_int, c_int, c_int, c_void,
+                                   c_void, c_void, c_size, c_void]),
+    "ic_block_mse_ws": (c_size, [c_int, c_int, c_int, c_int]),
+    "ic_block_mse_fwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll,
+                                 c_ll, c_void, c_void, c_size, c_void]),
+    "ic_block_mse_bwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_int, c_int, c_int, c_int, c_ll, c_ll,
+                                 c_ll, c_ll, c_void, c_void, c_void]),
 }
 
 _lib = None
@@ -249,6 +260,7 @@ stream_ops = _namespace("imgcomp_stream", "the segmented coder and the image bor
 mean_ops = _namespace("imgcomp_mean", "the mean-scale hyperprior's symbolizers, quantiser and reconstruction")
 ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, parameters and halves")
 gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel scaling")
+region_ops = _namespace("imgcomp_region", "scaling by a gain row per block and the block-weighted squared error")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

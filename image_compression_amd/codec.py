@@ -130,6 +130,31 @@ model.
                         the images of a call may differ), then the chunk lengths and payloads as in "ICRP".
 S >= 2 and a finite quality in [0, S-1], or the parser raises ValueError; a model with another S refuses the stream.
 The six containers do not read one another: every parser raises ValueError on another's magic.
+
+Region containers (little endian): `RegionGainedMeanScaleCompressor2018`, a quality per 64 x 64 pixel block
+------------------------------------------------------------------------------------------------------------
+A quality map is uint8 codes k[n, bi, bj], one per 64 x 64 block of the padded image: bi < H/64, bj < W/64.  The
+quality of a code, for a model with S levels, is
+    q(k) = fdiv(float32(k * (S - 1)), 255.0f)             (one correctly rounded float32 division of two exact integers)
+so q(0) = 0 and q(255) = S - 1 exactly, q is monotone in k, and an integer level s is a code exactly when
+255 % (S - 1) == 0 (the default S = 6: k = 51 s).  Position (i, j) of y belongs to block (i >> 2, j >> 2), position
+(i, j) of z is block (i, j).  Both sides obtain the gains in the same way:
+    1. U = the distinct codes of the call (of the group of streams decoded together), ascending;
+    2. the gain-vector rule above at the qualities [q(u) for u in U], by the same kernel: R = len(U) <= 256 rows per
+       table;
+    3. every position takes the row whose index is the rank of its block's code in U.
+A row is a function of its code alone, so the gains of an image do not depend on what else is coded or decoded with
+it, and a uniform map of code k holds bit for bit the gains of the gained model at quality q(k).  The symbols, h_s,
+the tables, rows, chunks and payloads are those of the gained streams with the gain vectors taken per position.
+    "ICRM" (batch):     the "ICRA" header with this magic, format version 1, then u32 S, u32 map_h, u32 map_w,
+                        then N * map_h * map_w code bytes in (n, bi, bj) order,
+                        then the chunk lengths and payloads as in "ICRA";
+    "ICRR" (per image): the "ICRP" header with this magic, format version 1, then u32 S, u32 map_h, u32 map_w,
+                        then map_h * map_w code bytes in (bi, bj) order (this image's map),
+                        then the chunk lengths and payloads as in "ICRP".
+The conditional kind is 2 or 3.  S >= 2, map_h == H/64 and map_w == W/64, and the buffer holds the whole map, or the
+parser raises ValueError; a model with another S refuses the stream.  The decoder takes the map from the stream.
+The eight containers do not read one another: every parser raises ValueError on another's magic.
 """
 import math
 import struct
@@ -168,6 +193,14 @@ GAINED_IMAGE_MAGIC = b"ICRQ"
 GAINED_FORMAT_VERSION = 1
 _GAINED_HEAD = struct.Struct(_FIELDS + "II" + "If")               # the ICRA header, then the gain levels and the quality
 _GAINED_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II" + "If")  # the ICRP header, then the same two
+
+REGION_MAGIC = b"ICRM"
+REGION_IMAGE_MAGIC = b"ICRR"
+REGION_FORMAT_VERSION = 1
+MAP_BLOCK = Z_DOWN         # a quality-map block is 64 x 64 pixels: one position of z, 4 x 4 of y
+MAP_CODE_MAX = 255
+_REGION_HEAD = struct.Struct(_FIELDS + "II" + "III")               # the ICRA header, then the gain levels and the map's shape
+_REGION_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II" + "III")  # the ICRP header, then the same three
 
 
 @dataclass
@@ -226,6 +259,39 @@ class GainedImageHeader(ImageHeader):
     quality: float
 
 
+class _MapEq:
+    """Equality of the region headers: field by field, the code maps as arrays."""
+
+    def __eq__(self, other):
+        if type(other) is not type(self):
+            return NotImplemented
+        a, b = dict(vars(self)), dict(vars(other))
+        ca, cb = a.pop("codes"), b.pop("codes")
+        return a == b and (ca is cb or (ca is not None and cb is not None and np.array_equal(ca, cb)))
+
+    __hash__ = None
+
+
+@dataclass(eq=False)
+class RegionHeader(_MapEq, Header):
+    """Header of the region batch container: the model's number of gain levels S, the shape of the quality map and
+    its codes, uint8 (N, map_h, map_w)."""
+    levels: int
+    map_h: int
+    map_w: int
+    codes: np.ndarray = None
+
+
+@dataclass(eq=False)
+class RegionImageHeader(_MapEq, ImageHeader):
+    """Header of the region per-image container: ImageHeader, then the levels, the map's shape and this image's codes,
+    uint8 (map_h, map_w)."""
+    levels: int
+    map_h: int
+    map_w: int
+    codes: np.ndarray = None
+
+
 def padded_size(h, w):
     """(H, W): h and w rounded up to multiples of 64, the size that is coded."""
     return -(-int(h) // Z_DOWN) * Z_DOWN, -(-int(w) // Z_DOWN) * Z_DOWN
@@ -280,14 +346,15 @@ def _whole_y(h):
     return (h.nsym_y,)
 
 
-def _fixed_bytes(head, h, y_symbols=_whole_y):
+def _fixed_bytes(head, h, y_symbols=_whole_y, var=0):
     nc = sum(num_chunks(n, h.R) for n in (h.nsym_z, *y_symbols(h)))
-    return head.size + 4 * nc + CHUNK_HEAD * nc
+    return head.size + var + 4 * nc + CHUNK_HEAD * nc
 
 
-def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y",), y_symbols=_whole_y):
+def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y",), y_symbols=_whole_y, var=b""):
     """One bytes object from the header `h`, which `check` passes, the streams' chunk-length tables and their
-    payloads; `extra`: the header fields after the chunk counts."""
+    payloads; `extra`: the header fields after the chunk counts; `var`: the bytes of the header's variable-length
+    section, between the fixed header and the tables."""
     check(h)
     lens = [np.ascontiguousarray(l, dtype="<u4") for l in lens]
     payloads = [bytes(p) for p in payloads]
@@ -297,13 +364,16 @@ def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y"
         raise ValueError("codec: chunk lengths do not add up to the payload")
     fields = (COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W, h.latent_channels, h.hyper_channels,
               h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y, h.nsym_z, h.nsym_y, *map(len, lens), *extra)
-    return b"".join([head.pack(magic, version, *fields)] + [l.tobytes() for l in lens] + payloads)
+    return b"".join([head.pack(magic, version, *fields), bytes(var)] + [l.tobytes() for l in lens] + payloads)
 
 
-def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_names=("y",), y_symbols=_whole_y, note=""):
+def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_names=("y",), y_symbols=_whole_y, note="",
+           var=None):
     """(header, the streams' chunk-length tables, their payloads) of a container: the header `head` with its magic
     and version, the header object `header(common fields, fields after the chunk counts)` passed through `check`,
-    and every check of the counts, the tables and the payload.  `note` ends the message about the symbol counts."""
+    and every check of the counts, the tables and the payload.  `note` ends the message about the symbol counts.
+    `var` = (size, take): the header has a variable-length section of `size(h)` bytes after its fixed part, which
+    `take(h, bytes)` stores in the checked header."""
     data = bytes(data)
     if len(data) < head.size:
         raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({head.size})")
@@ -330,6 +400,12 @@ def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_name
     if any(c != num_chunks(n, R) for c, n in zip(counts, nsyms)):
         raise ValueError("codec: chunk counts do not match the symbol counts")
     off = head.size
+    if var is not None:
+        size, take = var
+        if len(data) < off + size(h):
+            raise ValueError(f"codec: buffer ends inside the header's variable-length section of {size(h)} bytes")
+        take(h, data[off:off + size(h)])
+        off += size(h)
     if len(data) < off + 4 * sum(counts):
         raise ValueError("codec: buffer ends inside the chunk-length tables")
     tables = []
@@ -531,6 +607,132 @@ def parse_gained_image(data, abi, compute_dtype):
     checks of `parse_image`, and those of the levels and the quality.  Nothing is launched here."""
     return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION,
                   GainedImageHeader, _check_gained_image_header)
+
+
+# ---- region containers "ICRM" (batch) and "ICRR" (per image): the gained streams with a quality per 64 x 64 block
+def _check_levels(S):
+    if isinstance(S, bool) or int(S) != S or S < 2:
+        raise ValueError(f"codec: {S} gain levels (at least 2)")
+    return int(S)
+
+
+def code_quality(k, S):
+    """The float32 quality of the code k (0 .. 255) for a model with S levels, as a Python float: one correctly
+    rounded float32 division of k * (S - 1) by 255.  An array of codes gives a float32 array."""
+    S = _check_levels(S)
+    a = np.asarray(k)
+    if a.dtype.kind not in "iu" or a.size and (a.min() < 0 or a.max() > MAP_CODE_MAX):
+        raise ValueError(f"codec: a quality code is an integer in [0, {MAP_CODE_MAX}], got {k!r}")
+    q = (a.astype(np.int64) * (S - 1)).astype(np.float32) / np.float32(MAP_CODE_MAX)
+    return float(q) if a.ndim == 0 else q
+
+
+def quality_code(q, S):
+    """The code nearest to the quality q in [0, S-1]: rint(q * 255 / (S - 1)), ties to even.  ValueError outside the
+    range, NaN included."""
+    S = _check_levels(S)
+    try:
+        v = float("nan") if isinstance(q, (bool, str, bytes)) else float(q)
+    except (TypeError, ValueError):
+        raise ValueError(f"codec: a quality is a number in [0, {S - 1}], got {q!r}") from None
+    if not 0.0 <= v <= S - 1:    # NaN fails both comparisons
+        raise ValueError(f"codec: quality {q!r} is outside [0, {S - 1}]")
+    return int(np.rint(v * MAP_CODE_MAX / (S - 1)))
+
+
+def block_map(h, w, S, background, regions=()):
+    """The code map (ceil(h / 64), ceil(w / 64)), uint8, of an h x w image: `background` everywhere, and for every
+    (top, left, height, width, quality) pixel rectangle of `regions` each block it touches raised to the rectangle's
+    code -- a block takes the largest quality that touches it, the background's included.  ValueError for a
+    rectangle that is empty or leaves the image."""
+    h, w = int(h), int(w)
+    if h < 1 or w < 1:
+        raise ValueError(f"codec: no quality map of a {h} x {w} image")
+    codes = np.full((-(-h // MAP_BLOCK), -(-w // MAP_BLOCK)), quality_code(background, S), dtype=np.uint8)
+    for top, left, height, width, quality in regions:
+        top, left, height, width = int(top), int(left), int(height), int(width)
+        if height < 1 or width < 1 or top < 0 or left < 0 or top + height > h or left + width > w:
+            raise ValueError(f"codec: rectangle {(top, left, height, width)} is empty or leaves the {h} x {w} image")
+        blk = codes[top // MAP_BLOCK:(top + height - 1) // MAP_BLOCK + 1, left // MAP_BLOCK:(left + width - 1) // MAP_BLOCK + 1]
+        np.maximum(blk, np.uint8(quality_code(quality, S)), out=blk)
+    return codes
+
+
+def _check_map(h, shape):
+    if h.levels < 2:
+        raise ValueError(f"codec: {h.levels} gain levels (at least 2)")
+    if (h.map_h, h.map_w) != (h.H // MAP_BLOCK, h.W // MAP_BLOCK):
+        raise ValueError(f"codec: a {h.map_h} x {h.map_w} quality map for a {h.H} x {h.W} image, which has "
+                         f"{h.H // MAP_BLOCK} x {h.W // MAP_BLOCK} blocks")
+    if not h.kind & KIND_MEAN:
+        raise ValueError(f"codec: conditional kind {h.kind} in a region stream, which codes y about a mean (2 or 3)")
+    if h.codes is not None and (not isinstance(h.codes, np.ndarray) or h.codes.dtype != np.uint8 or h.codes.shape != shape):
+        raise ValueError(f"codec: the quality map must be uint8 codes of shape {shape}")
+
+
+def _check_region_header(h):
+    _check_header(h)
+    _check_map(h, (h.N, h.map_h, h.map_w))
+
+
+def _check_region_image_header(h):
+    _check_image_header(h)
+    _check_map(h, (h.map_h, h.map_w))
+
+
+def _map_bytes(h):
+    return h.N * h.map_h * h.map_w
+
+
+def _take_map(image):
+    def take(h, data):
+        h.codes = np.frombuffer(data, dtype=np.uint8).reshape((h.map_h, h.map_w) if image else (h.N, h.map_h, h.map_w))
+    return take
+
+
+def _packed_map(h):
+    if h.codes is None:
+        raise ValueError("codec: a region header without its quality map")
+    return np.ascontiguousarray(h.codes).tobytes()
+
+
+def region_fixed_bytes(h):
+    """`fixed_bytes` of a region batch container, the code map included."""
+    return _fixed_bytes(_REGION_HEAD, h, var=_map_bytes(h))
+
+
+def region_image_fixed_bytes(h):
+    """`fixed_bytes` of a region per-image container, the code map included."""
+    return _fixed_bytes(_REGION_IMAGE_HEAD, h, var=_map_bytes(h))
+
+
+def pack_region(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object from a RegionHeader, the two chunk-length tables and the two payloads."""
+    _check_region_header(h)
+    return _pack(_REGION_HEAD, REGION_MAGIC, REGION_FORMAT_VERSION, _check_region_header, h, (lens_z, lens_y),
+                 (payload_z, payload_y), (h.levels, h.map_h, h.map_w), var=_packed_map(h))
+
+
+def parse_region(data, abi, compute_dtype):
+    """(RegionHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_region`: the checks of
+    `parse`, and those of the levels and the map.  Nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _REGION_HEAD, REGION_MAGIC, REGION_FORMAT_VERSION, RegionHeader,
+                  _check_region_header, var=(_map_bytes, _take_map(False)))
+
+
+def pack_region_image(h, lens_z, lens_y, payload_z, payload_y):
+    """One bytes object for one image from its RegionImageHeader, chunk-length tables and payloads."""
+    _check_region_image_header(h)
+    return _pack(_REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, REGION_FORMAT_VERSION, _check_region_image_header, h,
+                 (lens_z, lens_y), (payload_z, payload_y), (h.height, h.width, h.levels, h.map_h, h.map_w),
+                 var=_packed_map(h))
+
+
+def parse_region_image(data, abi, compute_dtype):
+    """(RegionImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_region_image`: the
+    checks of `parse_image`, and those of the levels and the map.  Nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, REGION_FORMAT_VERSION,
+                  RegionImageHeader, _check_region_image_header, var=(_map_bytes, _take_map(True)))
 
 
 def split_packed_seg(packed, nseg, seg_len, R):

@@ -1650,6 +1650,143 @@ std::tuple<Tensor, Tensor> channel_scale_bwd_meta(const Tensor& x, const Tensor&
   return {at::empty_like(x), at::empty_like(g)};
 }
 
+// ---------------------------------------------------------------- region-of-interest coding (imgcomp_region)
+// A latent is a contiguous (N, Hm, Wm, C) tensor; the gains (R, C); a block map a contiguous uint8 tensor
+// (N, ceil(Hm / 2^shift), ceil(Wm / 2^shift)) of ranks below R.  An image pair is (N, C, H, W) with shared strides,
+// its map (N, ceil(H / 64), ceil(W / 64)), its weights (R).
+int64_t map_extent(int64_t v, int64_t shift) { return (v + (int64_t(1) << shift) - 1) >> shift; }
+
+void check_region_shapes(const Tensor& x, const Tensor& g, const Tensor& idx, int64_t shift) {
+  TORCH_CHECK_VALUE(shift >= 0 && shift <= 6, "imgcomp_region: a block is 2^shift positions wide, shift in 0 .. 6, got ",
+                    shift);
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "imgcomp_region: x must be a non-empty contiguous "
+              "(N, Hm, Wm, C) tensor, got ", x.sizes());
+  TORCH_CHECK(g.dim() == 2 && g.is_contiguous() && g.size(1) == x.size(3) && g.size(0) >= 1 && g.size(0) <= 256,
+              "imgcomp_region: the gains ", g.sizes(), " must be contiguous (1 .. 256, C) for x ", x.sizes());
+  TORCH_CHECK(x.size(0) <= 65535 && x.numel() / x.size(0) <= INT_MAX, "imgcomp_region: x is too large: ", x.sizes());
+  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.dim() == 3 && idx.is_contiguous() && idx.size(0) == x.size(0) &&
+                  idx.size(1) == map_extent(x.size(1), shift) && idx.size(2) == map_extent(x.size(2), shift),
+              "imgcomp_region: the block map ", idx.sizes(), " must be contiguous uint8 (", x.size(0), ", ",
+              map_extent(x.size(1), shift), ", ", map_extent(x.size(2), shift), ") for x ", x.sizes(), " at shift ", shift);
+}
+
+void check_region(const Tensor& x, const Tensor& g, const Tensor& idx, int64_t shift) {
+  check_operand(x, "x");
+  check_operand(g, "g");
+  TORCH_CHECK(idx.is_cuda(), "imgcomp: the block map must be on a ROCm device, got ", idx.device());
+  check_region_shapes(x, g, idx, shift);
+  TORCH_CHECK(x.device() == g.device() && x.device() == idx.device(), "imgcomp_region: x, g and the block map must be on "
+              "one device");
+}
+
+Tensor block_scale(const Tensor& x, const Tensor& g, const Tensor& idx, int64_t shift) {
+  check_region(x, g, idx, shift);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor out = at::empty_like(x);
+  check_rc(ic_block_scale(x.data_ptr<float>(), g.data_ptr<float>(), (int)g.size(0), idx.data_ptr<uint8_t>(), (int)x.size(0),
+                          (int)x.size(1), (int)x.size(2), (int)x.size(3), (int)shift, out.data_ptr<float>(), stream_of(x)),
+           "block_scale");
+  return out;
+}
+
+std::tuple<Tensor, Tensor> block_scale_bwd(const Tensor& x, const Tensor& g, const Tensor& idx, const Tensor& dy,
+                                           int64_t shift) {
+  check_region(x, g, idx, shift);
+  check_operand(dy, "dy");
+  TORCH_CHECK(dy.sizes() == x.sizes() && dy.is_contiguous() && dy.device() == x.device(), "imgcomp_region: dy ",
+              dy.sizes(), " must be contiguous with the shape ", x.sizes(), " of x, on its device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor dx = at::empty_like(x), dg = at::empty_like(g);
+  const int N = (int)x.size(0), Hm = (int)x.size(1), Wm = (int)x.size(2), C = (int)x.size(3);
+  const size_t nb = ic_block_scale_bwd_ws(N, Hm, Wm, C, (int)shift);
+  Tensor ws = workspace(x, nb);
+  check_rc(ic_block_scale_bwd(x.data_ptr<float>(), g.data_ptr<float>(), (int)g.size(0), idx.data_ptr<uint8_t>(),
+                              dy.data_ptr<float>(), N, Hm, Wm, C, (int)shift, dx.data_ptr<float>(), dg.data_ptr<float>(),
+                              ws.data_ptr(), nb, stream_of(x)),
+           "block_scale_bwd");
+  return {dx, dg};
+}
+
+void check_block_mse_shapes(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx) {
+  TORCH_CHECK(a.dim() == 4 && a.numel() > 0 && a.is_non_overlapping_and_dense(), "imgcomp_region: the images must be "
+              "non-empty dense (N, C, H, W) tensors, got ", a.sizes());
+  TORCH_CHECK(b.sizes() == a.sizes() && b.strides() == a.strides(), "imgcomp_region: the two images must share shape "
+              "and strides: ", a.sizes(), " / ", a.strides(), " and ", b.sizes(), " / ", b.strides());
+  TORCH_CHECK(a.size(0) <= 65535 && a.numel() / a.size(0) <= INT_MAX, "imgcomp_region: the images are too large: ",
+              a.sizes());
+  TORCH_CHECK(w.dim() == 1 && w.is_contiguous() && w.size(0) >= 1 && w.size(0) <= 256, "imgcomp_region: the weights ",
+              w.sizes(), " must be a contiguous vector of 1 .. 256");
+  TORCH_CHECK(idx.scalar_type() == at::kByte && idx.dim() == 3 && idx.is_contiguous() && idx.size(0) == a.size(0) &&
+                  idx.size(1) == map_extent(a.size(2), 6) && idx.size(2) == map_extent(a.size(3), 6),
+              "imgcomp_region: the block map ", idx.sizes(), " must be contiguous uint8 (", a.size(0), ", ",
+              map_extent(a.size(2), 6), ", ", map_extent(a.size(3), 6), ") for images ", a.sizes());
+}
+
+void check_block_mse(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx) {
+  check_operand(a, "input");
+  check_operand(b, "target");
+  check_operand(w, "the weights");
+  TORCH_CHECK(idx.is_cuda(), "imgcomp: the block map must be on a ROCm device, got ", idx.device());
+  check_block_mse_shapes(a, b, w, idx);
+  TORCH_CHECK(a.device() == b.device() && a.device() == w.device() && a.device() == idx.device(),
+              "imgcomp_region: the images, the weights and the block map must be on one device");
+}
+
+// {weighted mean, plain mean} of the squared error
+Tensor block_mse_fwd(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx) {
+  check_block_mse(a, b, w, idx);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  Tensor out = at::empty({2}, a.options().memory_format(at::MemoryFormat::Contiguous));
+  const int N = (int)a.size(0), C = (int)a.size(1), H = (int)a.size(2), W = (int)a.size(3);
+  const size_t nb = ic_block_mse_ws(N, C, H, W);
+  Tensor ws = workspace(a, nb);
+  check_rc(ic_block_mse_fwd(a.data_ptr<float>(), b.data_ptr<float>(), w.data_ptr<float>(), (int)w.size(0),
+                            idx.data_ptr<uint8_t>(), N, C, H, W, a.stride(0), a.stride(1), a.stride(2), a.stride(3),
+                            out.data_ptr<float>(), ws.data_ptr(), nb, stream_of(a)),
+           "block_mse_fwd");
+  return out;
+}
+
+// (ga, gb); a gradient that is not wanted comes back empty (0 elements)
+std::tuple<Tensor, Tensor> block_mse_bwd(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx,
+                                         const Tensor& g, bool need_a, bool need_b) {
+  check_block_mse(a, b, w, idx);
+  check_operand(g, "gradient");
+  TORCH_CHECK(g.numel() == 1, "block_mse_bwd: the gradient of a scalar loss is one value");
+  TORCH_CHECK(need_a || need_b, "block_mse_bwd: no gradient is asked for");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  Tensor gc = g.contiguous();
+  Tensor ga = need_a ? at::empty_strided(a.sizes(), a.strides(), a.options()) : at::empty({0}, a.options());
+  Tensor gb = need_b ? at::empty_strided(a.sizes(), a.strides(), a.options()) : at::empty({0}, a.options());
+  check_rc(ic_block_mse_bwd(a.data_ptr<float>(), b.data_ptr<float>(), w.data_ptr<float>(), (int)w.size(0),
+                            idx.data_ptr<uint8_t>(), gc.data_ptr<float>(), (int)a.size(0), (int)a.size(1), (int)a.size(2),
+                            (int)a.size(3), a.stride(0), a.stride(1), a.stride(2), a.stride(3),
+                            need_a ? ga.data_ptr<float>() : nullptr, need_b ? gb.data_ptr<float>() : nullptr, stream_of(a)),
+           "block_mse_bwd");
+  return {ga, gb};
+}
+
+Tensor block_scale_meta(const Tensor& x, const Tensor& g, const Tensor& idx, int64_t shift) {
+  check_region_shapes(x, g, idx, shift);
+  return at::empty_like(x);
+}
+std::tuple<Tensor, Tensor> block_scale_bwd_meta(const Tensor& x, const Tensor& g, const Tensor& idx, const Tensor& dy,
+                                                int64_t shift) {
+  check_region_shapes(x, g, idx, shift);
+  TORCH_CHECK(dy.sizes() == x.sizes(), "imgcomp_region: dy ", dy.sizes(), " must have the shape ", x.sizes(), " of x");
+  return {at::empty_like(x), at::empty_like(g)};
+}
+Tensor block_mse_fwd_meta(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx) {
+  check_block_mse_shapes(a, b, w, idx);
+  return at::empty({2}, a.options().memory_format(at::MemoryFormat::Contiguous));
+}
+std::tuple<Tensor, Tensor> block_mse_bwd_meta(const Tensor& a, const Tensor& b, const Tensor& w, const Tensor& idx,
+                                              const Tensor& g, bool need_a, bool need_b) {
+  check_block_mse_shapes(a, b, w, idx);
+  return {need_a ? at::empty_strided(a.sizes(), a.strides(), a.options()) : at::empty({0}, a.options()),
+          need_b ? at::empty_strided(a.sizes(), a.strides(), a.options()) : at::empty({0}, a.options())};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -1978,4 +2115,27 @@ TORCH_LIBRARY_IMPL(imgcomp_gain, Meta, m) {
   m.impl("gain_vector_bwd", gain_vector_bwd_meta);
   m.impl("channel_scale", channel_scale_meta);
   m.impl("channel_scale_bwd", channel_scale_bwd_meta);
+}
+
+// Region-of-interest coding (RegionGainedMeanScaleCompressor2018): additive, in a namespace of its own.
+TORCH_LIBRARY(imgcomp_region, m) {
+  m.def("block_scale(Tensor x, Tensor g, Tensor idx, int shift) -> Tensor");
+  m.def("block_scale_bwd(Tensor x, Tensor g, Tensor idx, Tensor dy, int shift) -> (Tensor, Tensor)");
+  m.def("block_mse_fwd(Tensor a, Tensor b, Tensor w, Tensor idx) -> Tensor");
+  m.def("block_mse_bwd(Tensor a, Tensor b, Tensor w, Tensor idx, Tensor gout, bool need_a, bool need_b) -> "
+        "(Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_region, CUDA, m) {
+  m.impl("block_scale", block_scale);
+  m.impl("block_scale_bwd", block_scale_bwd);
+  m.impl("block_mse_fwd", block_mse_fwd);
+  m.impl("block_mse_bwd", block_mse_bwd);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_region, Meta, m) {
+  m.impl("block_scale", block_scale_meta);
+  m.impl("block_scale_bwd", block_scale_bwd_meta);
+  m.impl("block_mse_fwd", block_mse_fwd_meta);
+  m.impl("block_mse_bwd", block_mse_bwd_meta);
 }

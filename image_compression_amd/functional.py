@@ -976,6 +976,90 @@ def channel_scale(x, g):
     return ChannelScaleFn.apply(x, g)
 
 
+# ============================================================== region-of-interest coding
+def _block_map(idx, device):
+    """A block map as the kernels take it: contiguous uint8 on the device."""
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.uint8 or idx.dim() != 3:
+        raise ValueError("a block map is a uint8 tensor (N, blocks down, blocks across)")
+    if not idx.is_cuda:
+        raise RuntimeError(f"imgcomp: HIP kernels need tensors on a ROCm (cuda) device; got a block map on {idx.device}")
+    return idx.contiguous()
+
+
+class BlockScaleFn(Function):
+    """x (N, C, H, W) times row idx[n, i >> shift, j >> shift] of the gains g (R, C) at position (i, j): one fp32
+    multiplication per element (torch.ops.imgcomp_region.block_scale / block_scale_bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, g, idx, shift):
+        _lib.require_device(x, g)
+        shift = int(shift)
+        if x.dim() != 4 or g.dim() != 2 or g.shape[1] != x.shape[1] or not 1 <= g.shape[0] <= 256:
+            raise ValueError(f"the gains {tuple(g.shape)} must be (1 .. 256, C) for a tensor of shape {tuple(x.shape)}")
+        if not 0 <= shift <= 6:
+            raise ValueError(f"a block is 2^shift positions wide, shift in 0 .. 6, got {shift}")
+        idx = _block_map(idx, x.device)
+        want = (x.shape[0], -(-x.shape[2] >> shift), -(-x.shape[3] >> shift))
+        if tuple(idx.shape) != want:
+            raise ValueError(f"the block map {tuple(idx.shape)} must be {want} for a tensor of shape {tuple(x.shape)} at "
+                             f"shift {shift}")
+        xl, g = _to_last(x), g.contiguous()
+        ctx.save_for_backward(xl, g, idx)
+        ctx.shift = shift
+        return _from_last(_lib.region_ops().block_scale(xl, g, idx, shift))
+
+    @staticmethod
+    def backward(ctx, dy):
+        xl, g, idx = ctx.saved_tensors
+        dx, dg = _lib.region_ops().block_scale_bwd(xl, g, idx, _to_last(dy), ctx.shift)
+        return _from_last(dx), dg, None, None
+
+
+class BlockMSEFn(Function):
+    """(the mean of w[idx[n, i >> 6, j >> 6]] (a - b)^2, the plain mean of (a - b)^2) of two images (N, C, H, W), from
+    one pass; the second carries no gradient (torch.ops.imgcomp_region.block_mse_fwd / block_mse_bwd)."""
+
+    @staticmethod
+    def forward(ctx, a, b, w, idx):
+        _lib.require_device(a, b, w)
+        if a.dim() != 4 or w.dim() != 1 or not 1 <= w.shape[0] <= 256:
+            raise ValueError(f"block_mse takes images (N, C, H, W) and 1 .. 256 weights, got {tuple(a.shape)} and "
+                             f"{tuple(w.shape)}")
+        idx = _block_map(idx, a.device)
+        want = (a.shape[0], -(-a.shape[2] // 64), -(-a.shape[3] // 64))
+        if tuple(idx.shape) != want:
+            raise ValueError(f"the block map {tuple(idx.shape)} must be {want} for images of shape {tuple(a.shape)}")
+        a = _dense(a)
+        b = _match(b, a)
+        w = w.contiguous()
+        ctx.save_for_backward(a, b, w, idx)
+        out = _lib.region_ops().block_mse_fwd(a, b, w, idx)
+        weighted, plain = out[0], out[1]
+        ctx.mark_non_differentiable(plain)
+        return weighted, plain
+
+    @staticmethod
+    def backward(ctx, g, _g_plain):
+        a, b, w, idx = ctx.saved_tensors
+        need = ctx.needs_input_grad[:2]
+        if not any(need):
+            return None, None, None, None
+        ga, gb = _lib.region_ops().block_mse_bwd(a, b, w, idx, g, need[0], need[1])
+        return (ga if need[0] else None), (gb if need[1] else None), None, None
+
+
+def block_scale(x, g, idx, shift):
+    """x (N, C, H, W) scaled per channel by the row of g (R, C) its block names: idx uint8 (N, ceil(H / 2^shift),
+    ceil(W / 2^shift)) on the device (BlockScaleFn)."""
+    return BlockScaleFn.apply(x, g, idx, shift)
+
+
+def block_mse(a, b, w, idx):
+    """(block-weighted mean squared error, plain mean squared error) of two images: w (R) on the device, idx uint8
+    (N, ceil(H / 64), ceil(W / 64)) (BlockMSEFn)."""
+    return BlockMSEFn.apply(a, b, w, idx)
+
+
 class SqDiffFn(Function):
     """(a - b)^2 elementwise: nn.MSELoss(reduction='none')."""
 

@@ -1,0 +1,198 @@
+"""RegionGainedMeanScaleCompressor2018 -- region-of-interest coding on the gained mean-scale hyperprior: a quality
+per 64 x 64 pixel block instead of one per image, so that a face or a line of text is coded at quality 5 while the sky
+around it is coded at quality 1.
+
+The parameters and the state-dict keys are GainedMeanScaleCompressor2018's (a gained checkpoint loads with
+strict=True; a fresh model has the gained model's values from the same seed).  What changes is where the gain
+vectors come from.  A quality map is uint8 codes k[n, bi, bj] (codec.py: q(k) = k (S - 1) / 255 in float32); one
+block is one position of z and 4 x 4 positions of y.  Per call, on both sides of the codec:
+    U = the distinct codes, ascending;  rows = gain_vector(table, [q(u) for u in U]) for each of the four tables;
+    every position is scaled by the row whose index is the rank of its block's code (functional.block_scale, shift 0
+    on z and 2 on y).
+A uniform map of code k therefore holds bit for bit the gains of the gained model at quality q(k), and a two-region
+map costs the same four gain_vector launches as a scalar quality.
+
+Quality.  `set_quality_map(codes)`: uint8 codes (Hb, Wb) for every image of the batch or (N, Hb, Wb), numpy or torch,
+None to clear; (Hb, Wb) must be the call's padded size over 64 or the call raises ValueError before any launch.
+`set_quality(q)` is the uniform map of quality_code(q, S) sized to the call (a sequence: one uniform map per image of
+`compress_each`), and clears a map.  The decoders take the map from the stream ("ICRM" / "ICRR"), never from the model.
+
+Training.  Only the MSE with REDUCTION "mean": total_loss = block_mse(x, x~; w) + bpp with w[r] = loss_weight(q(U[r])),
+losses["MSE"] the plain mean (the kernel's second output).  With `sample_quality` (the default) every training
+forward draws one integer level per block, independent and uniform, from the CPU generator seeded with cfg.SEED
+(`last_quality`: the code map; no device draw, the Philox order z, then y is unchanged); otherwise it uses the map
+that was set, or the uniform map of `quality`.  H and W must be multiples of 64 in training mode.  The map changes on
+the host every step, which is why TrainStep(graph=True) refuses this model (`graph_refusal`)."""
+import numpy as np
+import torch
+
+from ... import codec as _codec
+from ...functional import block_mse, block_scale
+from .build import META_ARCH_REGISTRY
+from .gained2021 import GainedMeanScaleCompressor2018
+
+
+def _as_codes(codes):
+    """A quality map as a contiguous uint8 numpy array (Hb, Wb) or (N, Hb, Wb); ValueError for anything else."""
+    if isinstance(codes, torch.Tensor):
+        if codes.dtype != torch.uint8:
+            raise ValueError(f"a quality map holds uint8 codes, got {codes.dtype}")
+        codes = codes.detach().cpu().numpy()
+    codes = np.asarray(codes)
+    if codes.dtype != np.uint8 or codes.ndim not in (2, 3) or codes.size == 0:
+        raise ValueError(f"a quality map holds uint8 codes of shape (Hb, Wb) or (N, Hb, Wb), got {codes.dtype} "
+                         f"{codes.shape}")
+    return np.ascontiguousarray(codes).copy()
+
+
+@META_ARCH_REGISTRY.register()
+class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
+    graph_refusal = ("RegionGainedMeanScaleCompressor2018 draws its quality map and its block weights on the host every "
+                     "step: a captured graph would replay one map for ever; use TrainStep(graph=False)")
+
+    def __init__(self, cfg):
+        names, reduction = list(cfg.MODEL.LOSS.DISTORTION_LOSS_NAMES), cfg.MODEL.LOSS.REDUCTION
+        if names != ["MSE"] or reduction != "mean":
+            raise ValueError("RegionGainedMeanScaleCompressor2018 trains with the block-weighted MSE only: "
+                             f"DISTORTION_LOSS_NAMES [\"MSE\"] with REDUCTION \"mean\", got {names} with {reduction!r}")
+        super().__init__(cfg)
+        self._map = None
+        self._codes = self._idx = self._weights = None
+
+    # ---- quality
+    @property
+    def quality_map(self):
+        """The map that was set (a copy), or None."""
+        return None if self._map is None else self._map.copy()
+
+    def set_quality_map(self, codes):
+        """uint8 codes (Hb, Wb), shared by the batch, or (N, Hb, Wb); None: back to the uniform map of `quality`."""
+        self._map = None if codes is None else _as_codes(codes)
+
+    def set_quality(self, q):
+        super().set_quality(q)
+        self._map = None
+
+    def _one_quality(self, who):
+        return None if self._map is not None else super()._one_quality(who)
+
+    def _call_map(self, N, H, W, who, each=False):
+        """The codes (N, Hb, Wb) of a call on N images of padded size H x W; ValueError for a map of another shape."""
+        hb, wb = -(-H // _codec.MAP_BLOCK), -(-W // _codec.MAP_BLOCK)
+        if self._map is not None:
+            m = self._map
+            if m.shape[-2:] != (hb, wb) or (m.ndim == 3 and m.shape[0] != N):
+                raise ValueError(f"{who}: the quality map {m.shape} is not the call's: {N} images of {hb} x {wb} blocks "
+                                 f"(padded size {H} x {W} over {_codec.MAP_BLOCK})")
+            return np.ascontiguousarray(np.broadcast_to(m, (N, hb, wb)))
+        if each and isinstance(self._quality, list):
+            if len(self._quality) != N:
+                raise ValueError(f"compress_each: {len(self._quality)} qualities for {N} images")
+            ks = [_codec.quality_code(q, self.levels) for q in self._quality]
+        else:
+            ks = [_codec.quality_code(self._one_quality(who), self.levels)] * N
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(ks, dtype=np.uint8)[:, None, None], (N, hb, wb)))
+
+    def sample_map(self, N, hb, wb):
+        """The next code map of the training sampler: one integer level per block, independent and uniform over the S
+        levels (CPU generator, cfg.SEED)."""
+        levels = torch.randint(0, self.levels, (N, hb, wb), generator=self._sampler).numpy()
+        lut = np.asarray([_codec.quality_code(s, self.levels) for s in range(self.levels)], dtype=np.uint8)
+        return lut[levels]
+
+    def _use_map(self, codes, device, loss=False):
+        """The rows and the rank indices of a call: U = the distinct codes ascending, one gain row per code, and for
+        every block the rank of its code; `loss`: one distortion weight per code too (the forward)."""
+        codes = np.ascontiguousarray(codes, dtype=np.uint8)
+        U, ranks = np.unique(codes, return_inverse=True)
+        ranks = ranks.reshape(codes.shape).astype(np.uint8)
+        self._codes = codes
+        self._use([_codec.code_quality(int(u), self.levels) for u in U])
+        self._idx = torch.from_numpy(ranks).to(device)
+        if loss:
+            w = np.asarray([self.loss_weight(q) for q in self._qualities], dtype=np.float64)
+            self.distortion_loss_weight = float(w[ranks].mean())
+            self._weights = torch.from_numpy(w.astype(np.float32)).to(device)
+
+    def _clear(self):
+        self._gains = self._qualities = self._codes = self._idx = self._weights = None
+
+    # ---- the forward
+    def forward(self, x):
+        if x.dim() != 4:
+            raise ValueError(f"forward: image batch {tuple(x.shape)} must be (N, C, H, W)")
+        N, _, H, W = x.shape
+        if self.training and (H % _codec.MAP_BLOCK or W % _codec.MAP_BLOCK):
+            raise ValueError(f"forward: in training mode H and W must be multiples of {_codec.MAP_BLOCK} (whole blocks), "
+                             f"got {H} x {W}")
+        if not (self.training and self.sample_quality):
+            self._call_map(N, H, W, "forward")   # in front of any launch
+        return super().forward(x)
+
+    def _forward(self, x):
+        N, _, H, W = x.shape
+        if self.training and self.sample_quality:
+            codes = self.sample_map(N, H // _codec.MAP_BLOCK, W // _codec.MAP_BLOCK)
+        else:
+            codes = self._call_map(N, H, W, "forward")
+        self.last_quality = codes
+        try:
+            self._use_map(codes, x.device, loss=True)
+            return super(GainedMeanScaleCompressor2018, self)._forward(x)
+        finally:
+            self._clear()   # no graph kept alive by module state
+
+    def _hyper_gain(self, z):
+        return block_scale(z, self._gains[2], self._idx, 0)
+
+    def _hyper_ungain(self, z_hat):
+        return block_scale(z_hat, self._gains[3], self._idx, 0)
+
+    def _latent_gain(self, y):
+        return block_scale(y, self._gains[0], self._idx, 2)
+
+    def _latent_ungain(self, y_hat):
+        return block_scale(y_hat, self._gains[1], self._idx, 2)
+
+    def distortion_loss(self, img1, img2):
+        """{"MSE": (the block-weighted mean, the plain mean)} of one pass over the two images."""
+        return {"MSE": block_mse(img1, img2, self._weights, self._idx)}
+
+    def _losses(self, z_ce, y_ce, dist, num_pixels):
+        weighted, plain = dist["MSE"]
+        entropy = (z_ce + y_ce) / num_pixels
+        return {
+            "z_entropy": z_ce.detach() / num_pixels,
+            "y_entropy": y_ce.detach() / num_pixels,
+            "bpp": entropy.detach(),
+            "total_loss": weighted + entropy,
+            "MSE": plain.detach(),
+        }
+
+    # ---- bitstreams: containers "ICRM" and "ICRR" (codec.py)
+    _pack, _parse = staticmethod(_codec.pack_region), staticmethod(_codec.parse_region)
+    _pack_image, _parse_image = staticmethod(_codec.pack_region_image), staticmethod(_codec.parse_region_image)
+
+    def _codable(self):
+        super()._codable()
+        self._clear()
+
+    def compress_each(self, x, steps_per_chunk=1024):
+        if x.dim() == 4 and min(x.shape) >= 1:   # the map against the padded size, in front of any launch
+            self._call_map(x.shape[0], *_codec.padded_size(*x.shape[2:]), "compress_each", each=True)
+        return super().compress_each(x, steps_per_chunk)
+
+    def _analyse(self, x, each=False):
+        N, _, H, W = x.shape
+        self._use_map(self._call_map(N, H, W, "compress_each" if each else "compress", each), x.device)
+        return super(GainedMeanScaleCompressor2018, self)._analyse(x, each)
+
+    def _header(self, N, H, W, y, z, steps_per_chunk, kz, ky, size=None, image=0):
+        h = super(GainedMeanScaleCompressor2018, self)._header(N, H, W, y, z, steps_per_chunk, kz, ky, size)
+        codes = self._codes if size is None else self._codes[image]
+        return (_codec.RegionHeader if size is None else _codec.RegionImageHeader)(
+            **vars(h), levels=self.levels, map_h=codes.shape[-2], map_w=codes.shape[-1], codes=np.ascontiguousarray(codes))
+
+    def _begin_decode(self, headers):
+        codes = headers[0].codes if len(headers) == 1 and headers[0].codes.ndim == 3 else np.stack([h.codes for h in headers])
+        self._use_map(codes, next(self.parameters()).device)

@@ -633,6 +633,34 @@ size_t ic_channel_scale_bwd_ws(long long N, long long P, int C, int g_rows);
 int ic_channel_scale_bwd(const float* x, const float* g, const float* dy, long long N, long long P, int C, int g_rows,
                          float* dx, float* dg, void* ws, size_t ws_bytes, void* stream);
 
+/* ---- region-of-interest coding (additive to version 4; RegionGainedMeanScaleCompressor2018).  A block map `idx`
+ *      holds one uint8 rank per block of 2^shift x 2^shift positions, (N, ceil(Hm / 2^shift), ceil(Wm / 2^shift)):
+ *      position (i, j) of image n takes row idx[n, i >> shift, j >> shift] of R rows, 1 <= R <= 256.  A rank >= R is
+ *      clamped to R - 1.  IC_ERR_ARG before any launch for a null pointer, R outside 1 .. 256, N outside 1 .. 65535,
+ *      an extent below 1, Hm Wm C >= 2^31 or a shift outside 0 .. 6.  None of them allocates or waits for its stream; no
+ *      floating-point atomics, every sum in a fixed order. ---- */
+/* x, out: dense (N, Hm, Wm, C) storage, channel fastest; g: (R, C).  out[n,i,j,c] = x[n,i,j,c] * g[rank][c], one
+ * fp32 multiplication */
+int ic_block_scale(const float* x, const float* g, int R, const unsigned char* idx, int N, int Hm, int Wm, int C,
+                   int shift, float* out, void* stream);
+/* dx = dy * g[rank] and dg[r][c] = the sum of dy x over the positions whose block has rank r (+0.0 for a rank no
+ * block has): per block over its positions in ascending (i, j) into `ws`, then one thread per (r, c) over the blocks
+ * in ascending (n, bi, bj).  The query returns 0 for a shape the call refuses */
+size_t ic_block_scale_bwd_ws(int N, int Hm, int Wm, int C, int shift);
+int ic_block_scale_bwd(const float* x, const float* g, int R, const unsigned char* idx, const float* dy, int N, int Hm,
+                       int Wm, int C, int shift, float* dx, float* dg, void* ws, size_t ws_bytes, void* stream);
+/* a, b: images (N, C, H, W) that share the strides (sn, sc, sh, sw), each >= 1, C H W < 2^31; w: R weights on the
+ * device; idx: the pixel block map, shift 6.  out[0] = sum of w[rank] (a-b)^2 / n, out[1] = sum of (a-b)^2 / n,
+ * n = N C H W, from one pass */
+size_t ic_block_mse_ws(int N, int C, int H, int W);
+int ic_block_mse_fwd(const float* a, const float* b, const float* w, int R, const unsigned char* idx, int N, int C, int H,
+                     int W, long long sn, long long sc, long long sh, long long sw, float* out, void* ws, size_t ws_bytes,
+                     void* stream);
+/* ga = gout[0] 2 w[rank] (a-b) / n (NULL to skip), gb = -ga (NULL to skip; not both), with the inputs' strides */
+int ic_block_mse_bwd(const float* a, const float* b, const float* w, int R, const unsigned char* idx, const float* gout,
+                     int N, int C, int H, int W, long long sn, long long sc, long long sh, long long sw, float* ga,
+                     float* gb, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,12 @@ forward, compress and decompress at 1 x --height x --width (seed weights and zer
 symbols), the gain kernels beside ic_center_round by device events on the y of N images, one eager training step
 of both at 32 x 256 x 256, and the coded bytes at every integer level of a ladder of gains on --scale'd weights.
 
+--region N times GainedMeanScaleCompressor2018 (scalar quality 3) and RegionGainedMeanScaleCompressor2018 (a centre
+rectangle at level 5 over a background at level 1) alternately in one process, both on --scale'd weights with ladder
+tables: the eval forward, compress and decompress at 1 x --height x --width; ic_block_scale / _bwd beside
+ic_channel_scale / _bwd with a row per image and ic_block_mse beside ic_mse by device events on N images; one eager
+training step of both at 32 x 256 x 256; and the coded bytes of three maps.
+
 --context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
 --each works on it too (its loop arm is then the fused model's own compress / decompress).
 
@@ -196,9 +202,15 @@ def main():
                     help="MODEL.CONTEXT.KERNEL of CheckerboardCompressor2018")
     ap.add_argument("--context-compare", type=int, default=0, metavar="N", dest="context_compare",
                     help='the "conv" and the "fused" checkerboard model alternately; per-image streams at N images')
+    ap.add_argument("--region", type=int, default=0, metavar="N",
+                    help="GainedMeanScaleCompressor2018 and RegionGainedMeanScaleCompressor2018 alternately; kernels on "
+                         "the y of N images")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.region:
+        _emit(region_bench(args), args.out)
+        return
     if args.context_compare:
         _emit(context_bench(args), args.out)
         return
@@ -542,6 +554,125 @@ def gained_bench(args):
                            "kmax_y": h.kmax_y, "decompress_equals_forward": bool(torch.equal(x_hat, ms(x)[0])),
                            "mse": float(((x_hat - x) ** 2).mean())})
         out["ladder_0.3_per_level"], out["ladder_weight_scale"] = ladder, args.scale
+    # one eager training step of both at 32 x 256 x 256
+    xt = torch.rand(32, 3, 256, 256, device="cuda", generator=g)
+    steps = {a: TrainStep(_build(a, 1.0)[0].train(), xt, graph=False) for a in archs}
+    for _ in range(3):
+        for st in steps.values():
+            st()
+    t = {a: [] for a in archs}
+    for _ in range(reps):
+        for a, st in steps.items():
+            t[a].append(_wall(st, 1))
+    for a, v in t.items():
+        out[f"{a}_train_step_32x256x256_ms"] = round(min(v), 3)
+        out[f"{a}_train_step_32x256x256_all_ms"] = [round(u, 3) for u in v]
+    return out
+
+
+def region_bench(args):
+    """--region N: the gained model at a scalar quality and the region model at a two-code map, one repetition of
+    each at a time."""
+    import numpy as np
+    from image_compression_amd import _lib, codec
+    from image_compression_amd import functional as F
+    from image_compression_amd.step import TrainStep
+    archs = ("GainedMeanScaleCompressor2018", "RegionGainedMeanScaleCompressor2018")
+    GAINED, REGION = archs
+    H, W, reps, N = args.height, args.width, args.reps, args.region
+    hb, wb = H // 64, W // 64
+    g = torch.Generator(device="cuda").manual_seed(5)
+    out = {"metric": f"gained codec with a scalar quality and with a quality map at 3 x {H} x {W}, weight cache, best of "
+                     f"{reps} alternating reps", "unit": "ms", "reps": reps, "weight_scale": args.scale,
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0), "
+                   "ladder tables +-0.3 per level"}
+
+    def ladder(m):
+        for name, sign in (("log_y", 1.0), ("log_inv_y", -1.0), ("log_z", 1.0), ("log_inv_z", -1.0)):
+            getattr(m.gain, name).copy_(sign * 0.3 * torch.arange(m.levels, device="cuda").view(-1, 1))
+        return m
+
+    def centre(lo, hi):
+        """A centre rectangle of a quarter of the blocks at level `hi` over a background at level `lo`."""
+        return codec.block_map(H, W, 6, lo, [(64 * (hb // 4), 64 * (wb // 4), 64 * (hb // 2), 64 * (wb // 2), hi)])
+
+    x = torch.rand(1, 3, H, W, device="cuda", generator=g)
+    with torch.no_grad(), F.weight_cache():
+        models = {a: ladder(_build(a, args.scale)[0]) for a in archs}
+        models[GAINED].set_quality(3.0)
+        two = centre(1, 5)
+        models[REGION].set_quality_map(two)
+        out["map_codes"], out["map_blocks"] = sorted(set(two.reshape(-1).tolist())), [hb, wb]
+        data = {}
+        for a, m in models.items():
+            for _ in range(2):                               # warm-up of every candidate
+                data[a] = m.compress(x)
+                same = bool(torch.equal(m.decompress(data[a]), m(x)[0]))
+            out[f"{a}_decompress_equals_forward"] = same
+            out[f"{a}_bytes"] = len(data[a])
+        fns = {"forward": lambda m, a: m(x), "compress": lambda m, a: m.compress(x),
+               "decompress": lambda m, a: m.decompress(data[a])}
+        t = {(k, a): [] for k in fns for a in archs}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                for a, m in models.items():
+                    t[k, a].append(_wall(lambda: fn(m, a), 1))
+        for (k, a), v in t.items():
+            out[f"{a}_{k}_ms"] = round(min(v), 4)
+            out[f"{a}_{k}_all_ms"] = [round(u, 3) for u in v]
+        for k in fns:
+            out[f"region_minus_gained_{k}_ms"] = round(min(t[k, REGION]) - min(t[k, GAINED]), 4)
+            out[f"gained_{k}_scatter_ms"] = round(max(t[k, GAINED]) - min(t[k, GAINED]), 4)
+        # the kernels by device events on the y of N images; the candidates alternate inside every repetition
+        m = models[REGION]
+        gops, rops, ops = _lib.gain_ops(), _lib.region_ops(), _lib.ops()
+        xn = torch.rand(N, 3, H, W, device="cuda", generator=g)
+        y_l = m.analysis_transform(xn).movedim(1, -1).contiguous()
+        dy = torch.rand_like(y_l)
+        Cy = y_l.shape[-1]
+        gn = gops.gain_vector(m.gain.log_y, [float(n % 6) for n in range(N)])
+        g3 = gops.gain_vector(m.gain.log_y, [1.0, 2.686, 5.0])
+        idx = torch.randint(0, 3, (N, hb, wb), device="cuda", generator=g).to(torch.uint8)
+        w3 = torch.tensor([512.0, 1647.0, 8192.0], device="cuda")
+        xt = torch.rand(N, 3, H, W, device="cuda", generator=g)
+        one = torch.ones((), device="cuda")
+        calls = 20
+        kern = {   # name: (the call, bytes the kernel must move)
+            "channel_scale_per_image": (lambda: gops.channel_scale(y_l, gn), 8 * y_l.numel()),
+            "block_scale": (lambda: rops.block_scale(y_l, g3, idx, 2), 8 * y_l.numel()),
+            "channel_scale_bwd_per_image": (lambda: gops.channel_scale_bwd(y_l, gn, dy), 12 * y_l.numel()),
+            "block_scale_bwd": (lambda: rops.block_scale_bwd(y_l, g3, idx, dy, 2), 12 * y_l.numel()),
+            "mse_fwd": (lambda: ops.mse_fwd(xn, xt), 8 * xn.numel()),
+            "block_mse_fwd": (lambda: rops.block_mse_fwd(xn, xt, w3, idx), 8 * xn.numel()),
+            "mse_bwd": (lambda: ops.mse_bwd(xn, xt, one, False, True), 12 * xn.numel()),
+            "block_mse_bwd": (lambda: rops.block_mse_bwd(xn, xt, w3, idx, one, False, True), 12 * xn.numel()),
+        }
+        for fn, _ in kern.values():
+            fn()
+        tk = {k: [] for k in kern}
+        for _ in range(reps):
+            for k, (fn, _) in kern.items():
+                tk[k].append(_events(lambda: [fn() for _ in range(calls)], 1) / calls)
+        out["kernels_ms_per_call"] = {k: round(min(v), 5) for k, v in tk.items()}
+        out["kernels_all_ms_per_call"] = {k: [round(u, 5) for u in v] for k, v in tk.items()}
+        out["kernels_bytes"] = {k: b for k, (_, b) in kern.items()}
+        out["kernels_gb_per_s"] = {k: round(kern[k][1] / min(v) / 1e6, 1) for k, v in tk.items()}
+        out["kernels_latent_shape"], out["kernels_calls_between_events"] = list(y_l.shape), calls
+        ratio = min(tk["block_scale"]) / min(tk["channel_scale_per_image"])
+        out["block_scale_over_channel_scale"], out["block_scale_within_1.25x"] = round(ratio, 3), bool(ratio <= 1.25)
+        assert Cy == g3.shape[1]
+        # bytes following the map, on the ladder tables (a table, not a rate-distortion claim: no trained weights)
+        m = models[REGION]
+        rate = []
+        for name, codes in (("level 1 everywhere", centre(1, 1)), ("level 5 everywhere", centre(5, 5)),
+                            ("centre quarter at 5 over 1", two)):
+            m.set_quality_map(codes)
+            d = m.compress(x)
+            h = codec.parse_region(d, int(_lib.load().ic_version()), "fp32_split")[0]
+            rate.append({"map": name, "bytes": len(d), "coded_bpp": round(8 * len(d) / (H * W), 5), "kmax_z": h.kmax_z,
+                         "kmax_y": h.kmax_y, "blocks_at_5": int(np.sum(codes == 255)),
+                         "decompress_equals_forward": bool(torch.equal(m.decompress(d), m(x)[0]))})
+        out["rate_table"] = rate
     # one eager training step of both at 32 x 256 x 256
     xt = torch.rand(32, 3, 256, 256, device="cuda", generator=g)
     steps = {a: TrainStep(_build(a, 1.0)[0].train(), xt, graph=False) for a in archs}
