@@ -451,6 +451,9 @@ int wgrad_impl(const ic_act* G, const ic_act* X, int k, int stride, int pad, flo
     d.generic = 0;
     d.x3 = 0;
     d.bf16 = 0;
+    // the GEMM reads the column buffer (256-byte aligned in the workspace), never X itself: the kernel choice
+    // and its report must not see X's alignment
+    d.x = nullptr;
   }
   const size_t part = wg_plan(d);
   const size_t cs = db ? colsum_ws((long long)bias_src->n * bias_src->h * bias_src->w, bias_src->c) : 0;

@@ -1572,6 +1572,15 @@ size_t wg_plan(WgDesc& d) {
   d.mtiles = ic_cdiv(d.Cg, d.bm);
   d.ntiles = ic_cdiv(d.ncols, d.bn);
   d.P = (long long)d.N * d.Hg * d.Wg;
+  // bf16 operands run on the two-wave kernel only (wg_x3_launch's row-fast conditions; pps is a
+  // multiple of 32); elsewhere the split kernel when split arithmetic was asked for, else fp32.
+  // Decided before the pixel split: a launch that falls to the fp32 kernel takes that kernel's split, so it is
+  // the math-0 launch bit for bit
+  if (d.bf16 && !(d.x3 && WG_X3_DUAL && WG_X3_DUAL16 && d.Wg % 16 == 0 && (d.Wg % 32 == 0 || d.P % 32 == 0) &&
+                  (long long)d.gs_w * 16 < (1LL << 31) && (long long)d.stride * 16 * d.xs_w < (1LL << 31))) {
+    d.bf16 = 0;
+    if (!d.split_ok) d.x3 = 0;
+  }
   const long long tiles = (long long)d.mtiles * d.ntiles *
                           (d.generic ? 1 : d.T);
   // one full wave of blocks: 256 CUs x 2 resident blocks = 512 slots, so a
@@ -1587,13 +1596,6 @@ size_t wg_plan(WgDesc& d) {
   d.pps = (int)pps;
   d.nsplit = (int)((d.P + pps - 1) / pps);
   if (d.nsplit < 1) d.nsplit = 1;
-  // bf16 operands run on the two-wave kernel only (wg_x3_launch's row-fast conditions; pps is a
-  // multiple of 32); elsewhere the split kernel when split arithmetic was asked for, else fp32
-  if (d.bf16 && !(d.x3 && WG_X3_DUAL && WG_X3_DUAL16 && d.Wg % 16 == 0 && (d.Wg % 32 == 0 || d.P % 32 == 0) &&
-                  (long long)d.gs_w * 16 < (1LL << 31) && (long long)d.stride * 16 * d.xs_w < (1LL << 31))) {
-    d.bf16 = 0;
-    if (!d.split_ok) d.x3 = 0;
-  }
   const int Tp = d.generic ? 1 : d.T;
   const size_t slab = (size_t)d.nsplit * Tp * (size_t)d.Cg * d.ncols * sizeof(float);
   const int G = (d.nsplit + WG_SPG - 1) / WG_SPG;
