@@ -238,6 +238,10 @@ SIGNATURES = {
                                  c_ll, c_void, c_void, c_size, c_void]),
     "ic_block_mse_bwd": (c_int, [c_void, c_void, c_void, c_int, c_void, c_void, c_int, c_int, c_int, c_int, c_ll, c_ll,
                                  c_ll, c_ll, c_void, c_void, c_void]),
+    # rate and distortion maps: the estimated bits and the squared error of every block (additive to ic_version 4)
+    "ic_block_bits": (c_int, [c_void, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_int, c_void, c_void, c_void]),
+    "ic_block_sse": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll,
+                             c_int, c_void, c_void]),
 }
 
 _lib = None
@@ -261,6 +265,7 @@ mean_ops = _namespace("imgcomp_mean", "the mean-scale hyperprior's symbolizers, 
 ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, parameters and halves")
 gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel scaling")
 region_ops = _namespace("imgcomp_region", "scaling by a gain row per block and the block-weighted squared error")
+map_ops = _namespace("imgcomp_map", "the estimated bits and the squared error of every block")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

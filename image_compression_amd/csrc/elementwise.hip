@@ -2,11 +2,12 @@
 // All operate on dense storage of n fp32 elements; float4 vectorised where the
 // pointer alignment allows (Guideline 13), grid-stride otherwise.
 #include "../../include/imgcomp.h"
+#include "bits_term.h"
 #include "common.h"
 
 namespace {
 
-constexpr float LN2F = 0.693147180559945309f;
+constexpr float LN2F = IC_LN2F;
 
 inline unsigned grid_for(long long n, int per_thread = 1) {
   long long b = (n / per_thread + 255) / 256;
@@ -142,9 +143,8 @@ constexpr int RED_BLOCKS = 1024;
 
 template <int OP>
 __device__ __forceinline__ float red_term(const float* a, const float* b, long long i) {
-  if (OP == 0) {  // ce: clamp(-ln(p + 1e-10)/ln2, 0, 50)
-    const float t = -logf(a[i] + 1e-10f) / LN2F;
-    return fminf(fmaxf(t, 0.f), 50.f);
+  if (OP == 0) {  // ce: clamp(-ln(p + 1e-10)/ln2, 0, 50), the term of ic_block_bits too (bits_term.h)
+    return ic_bits_term(a[i]);
   } else {  // squared error
     const float d = a[i] - b[i];
     return d * d;

@@ -1787,6 +1787,89 @@ std::tuple<Tensor, Tensor> block_mse_bwd_meta(const Tensor& a, const Tensor& b, 
           need_b ? at::empty_strided(a.sizes(), a.strides(), a.options()) : at::empty({0}, a.options())};
 }
 
+// ---------------------------------------------------------------- rate and distortion maps (imgcomp_map)
+// A tensor is the logical (N, C, H, W); inside an image its storage is dense channels-last or dense NCHW (the stride
+// of an extent of 1 is not looked at).  A map is contiguous (N, ceil(H / 2^shift), ceil(W / 2^shift)).  Inference
+// only: no autograd node.
+bool map_layout_ok(const Tensor& t) {
+  const int64_t C = t.size(1), H = t.size(2), W = t.size(3), sc = t.stride(1), sh = t.stride(2), sw = t.stride(3);
+  const bool last = (C == 1 || sc == 1) && (W == 1 || sw == C) && (H == 1 || sh == W * C);
+  const bool nchw = (W == 1 || sw == 1) && (H == 1 || sh == W) && (C == 1 || sc == H * W);
+  return last || nchw;
+}
+
+void check_map_shapes(const Tensor& t, int64_t shift, const char* what) {
+  TORCH_CHECK_VALUE(shift >= 0 && shift <= 6, "imgcomp_map: a block is 2^shift positions wide, shift in 0 .. 6, got ",
+                    shift);
+  TORCH_CHECK(t.dim() == 4 && t.numel() > 0, "imgcomp_map: ", what, " must be a non-empty (N, C, H, W) tensor, got ",
+              t.sizes());
+  TORCH_CHECK(t.size(0) <= 65535 && t.numel() / t.size(0) <= INT_MAX, "imgcomp_map: ", what, " is too large: ", t.sizes());
+}
+
+void check_map_operand(const Tensor& t, const char* what) {
+  check_operand(t, what);
+  TORCH_CHECK(map_layout_ok(t) && t.stride(0) >= 0, "imgcomp_map: every image of ", what, " must be dense channels-last "
+              "or dense NCHW storage, got sizes ", t.sizes(), " with strides ", t.strides());
+}
+
+Tensor new_map(const Tensor& t, int64_t shift) {
+  return at::empty({t.size(0), map_extent(t.size(2), shift), map_extent(t.size(3), shift)},
+                   t.options().memory_format(at::MemoryFormat::Contiguous));
+}
+
+void check_map_add(const Tensor& p, int64_t shift, const std::optional<Tensor>& add) {
+  if (!add.has_value() || !add->defined()) return;
+  TORCH_CHECK(add->dim() == 3 && add->size(0) == p.size(0) && add->size(1) == map_extent(p.size(2), shift) &&
+                  add->size(2) == map_extent(p.size(3), shift) && add->is_contiguous(),
+              "imgcomp_map: add ", add->sizes(), " must be a contiguous map (", p.size(0), ", ",
+              map_extent(p.size(2), shift), ", ", map_extent(p.size(3), shift), ") of p ", p.sizes(), " at shift ", shift);
+}
+
+Tensor map_block_bits(const Tensor& p, int64_t shift, const std::optional<Tensor>& add) {
+  check_map_shapes(p, shift, "p");
+  check_map_operand(p, "p");
+  check_map_add(p, shift, add);
+  if (add.has_value() && add->defined()) {
+    check_operand(*add, "add");
+    TORCH_CHECK(add->device() == p.device(), "imgcomp_map: p and add must be on one device");
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(p.device());
+  Tensor out = new_map(p, shift);
+  check_rc(ic_block_bits(p.data_ptr<float>(), (int)p.size(0), (int)p.size(1), (int)p.size(2), (int)p.size(3), p.stride(0),
+                         p.stride(1), p.stride(2), p.stride(3), (int)shift, opt_ptr(add), out.data_ptr<float>(),
+                         stream_of(p)),
+           "block_bits");
+  return out;
+}
+
+Tensor map_block_sse(const Tensor& a, const Tensor& b, int64_t shift) {
+  check_map_shapes(a, shift, "a");
+  TORCH_CHECK(b.sizes() == a.sizes(), "imgcomp_map: the two images must share a shape, got ", a.sizes(), " and ",
+              b.sizes());
+  check_map_operand(a, "a");
+  check_map_operand(b, "b");
+  TORCH_CHECK(a.device() == b.device(), "imgcomp_map: the two images must be on one device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(a.device());
+  Tensor out = new_map(a, shift);
+  check_rc(ic_block_sse(a.data_ptr<float>(), b.data_ptr<float>(), (int)a.size(0), (int)a.size(1), (int)a.size(2),
+                        (int)a.size(3), a.stride(0), a.stride(1), a.stride(2), a.stride(3), b.stride(0), b.stride(1),
+                        b.stride(2), b.stride(3), (int)shift, out.data_ptr<float>(), stream_of(a)),
+           "block_sse");
+  return out;
+}
+
+Tensor map_block_bits_meta(const Tensor& p, int64_t shift, const std::optional<Tensor>& add) {
+  check_map_shapes(p, shift, "p");
+  check_map_add(p, shift, add);
+  return new_map(p, shift);
+}
+Tensor map_block_sse_meta(const Tensor& a, const Tensor& b, int64_t shift) {
+  check_map_shapes(a, shift, "a");
+  TORCH_CHECK(b.sizes() == a.sizes(), "imgcomp_map: the two images must share a shape, got ", a.sizes(), " and ",
+              b.sizes());
+  return new_map(a, shift);
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -2138,4 +2221,20 @@ TORCH_LIBRARY_IMPL(imgcomp_region, Meta, m) {
   m.impl("block_scale_bwd", block_scale_bwd_meta);
   m.impl("block_mse_fwd", block_mse_fwd_meta);
   m.impl("block_mse_bwd", block_mse_bwd_meta);
+}
+
+// Rate and distortion maps (Compressor2018.rate_distortion_map): additive, in a namespace of their own.
+TORCH_LIBRARY(imgcomp_map, m) {
+  m.def("block_bits(Tensor p, int shift, Tensor? add=None) -> Tensor");
+  m.def("block_sse(Tensor a, Tensor b, int shift) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_map, CUDA, m) {
+  m.impl("block_bits", map_block_bits);
+  m.impl("block_sse", map_block_sse);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_map, Meta, m) {
+  m.impl("block_bits", map_block_bits_meta);
+  m.impl("block_sse", map_block_sse_meta);
 }

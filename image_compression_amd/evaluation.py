@@ -242,3 +242,38 @@ class Evaluator:
         finally:
             self.model.train(was_training)
         return self.monitor.eval()
+
+    def run_eval_each(self, batches):
+        """One dict per image of the batches, in order, from `model.rate_distortion_map` (any image size; eager, no
+        coder): bpp = the estimated bits over the image's h w pixels, y_bpp and z_bpp its two parts, mse over the
+        real pixels and psnr = 10 log10(1 / mse) (inf at 0), worst_block = (bi, bj) of the 64 x 64 block with the
+        largest squared error per pixel, and quality where the model has one.  The sums over a map are taken on
+        the host in float64."""
+        import math
+
+        import numpy as np
+        was_training = self.model.training
+        self.model.eval()
+        scope = F.weight_cache() if self.weight_cache else contextlib.nullcontext()
+        out = []
+        try:
+            with scope:
+                for imgs in batches:
+                    if self.device is not None:
+                        imgs = imgs.to(self.device, non_blocking=True)
+                    rd = self.model.rate_distortion_map(imgs)
+                    n_pix = imgs.shape[2] * imgs.shape[3]
+                    by, bz, bits, sse = (t.double().cpu().numpy() for t in (rd.bits_y, rd.bits_z, rd.bits, rd.sse))
+                    for n in range(imgs.shape[0]):
+                        mse = float(sse[n].sum()) / (imgs.shape[1] * n_pix)
+                        worst = np.unravel_index(int(np.argmax(sse[n] / rd.pixels)), rd.pixels.shape)
+                        res = {"bpp": float(bits[n].sum()) / n_pix, "y_bpp": float(by[n].sum()) / n_pix,
+                               "z_bpp": float(bz[n].sum()) / n_pix, "mse": mse,
+                               "psnr": 10.0 * math.log10(1.0 / mse) if mse > 0.0 else math.inf,
+                               "worst_block": (int(worst[0]), int(worst[1]))}
+                        if hasattr(self.model, "quality"):
+                            res["quality"] = self.model.quality
+                        out.append(res)
+        finally:
+            self.model.train(was_training)
+        return out

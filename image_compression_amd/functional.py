@@ -1060,6 +1060,63 @@ def block_mse(a, b, w, idx):
     return BlockMSEFn.apply(a, b, w, idx)
 
 
+# ============================================================== rate and distortion maps
+def _map_operand(t, who, what):
+    """A map kernel's operand: fp32 (N, C, H, W) on the device; every image dense channels-last or dense NCHW storage
+    as it comes, a dense copy otherwise."""
+    _lib.require_device(t)
+    if t.dim() != 4 or t.numel() == 0:
+        raise ValueError(f"{who}: {what} must be a non-empty (N, C, H, W) tensor, got {tuple(t.shape)}")
+    t = t.detach()
+    (_, C, H, W), (_, sc, sh, sw) = t.shape, t.stride()
+    last = (C == 1 or sc == 1) and (W == 1 or sw == C) and (H == 1 or sh == W * C)
+    nchw = (W == 1 or sw == 1) and (H == 1 or sh == W) and (C == 1 or sc == H * W)
+    return t if last or nchw else t.contiguous()
+
+
+def _inference_only(who, **operands):
+    """RuntimeError if autograd would have to record the call: the map kernels have no backward."""
+    for what, t in operands.items():
+        if t is not None and t.requires_grad and torch.is_grad_enabled():
+            raise RuntimeError(f"{who} is inference only: {what} requires grad; detach it or call under torch.no_grad()")
+
+
+def _map_shift(shift):
+    shift = int(shift)
+    if not 0 <= shift <= 6:
+        raise ValueError(f"a block is 2^shift positions wide, shift in 0 .. 6, got {shift}")
+    return shift
+
+
+def block_bits(p, shift, add=None):
+    """The estimated bits of every block of 2^shift x 2^shift positions of the likelihoods p (N, C, H, W): the sum over
+    the block and all channels of clamp(-log2(p + 1e-10), 0, 50), CELossFn's term, as (N, ceil(H / 2^shift),
+    ceil(W / 2^shift)); with `add`, a map of that shape, add + that sum (one fp32 addition).  Inference only: no
+    autograd node.  Image n's map has the same bits whatever the batch around it
+    (torch.ops.imgcomp_map.block_bits)."""
+    _inference_only("block_bits", p=p, add=add)
+    p, shift = _map_operand(p, "block_bits", "p"), _map_shift(shift)
+    if add is not None:
+        _lib.require_device(add)
+        want = (p.shape[0], -(-p.shape[2] >> shift), -(-p.shape[3] >> shift))
+        if tuple(add.shape) != want:
+            raise ValueError(f"block_bits: add {tuple(add.shape)} must be the map {want} of p {tuple(p.shape)} at shift "
+                             f"{shift}")
+        add = add.detach().contiguous()
+    return _lib.map_ops().block_bits(p, shift, add)
+
+
+def block_sse(a, b, shift=6):
+    """The squared error of every block of 2^shift x 2^shift pixels of two images (N, C, H, W): the sum of (a - b)^2
+    over the block and all channels, as (N, ceil(H / 2^shift), ceil(W / 2^shift)).  Inference only: no autograd node.
+    Image n's map has the same bits whatever the batch around it (torch.ops.imgcomp_map.block_sse)."""
+    _inference_only("block_sse", a=a, b=b)
+    a, b = _map_operand(a, "block_sse", "a"), _map_operand(b, "block_sse", "b")
+    if a.shape != b.shape:
+        raise ValueError(f"block_sse: the two images must share a shape, got {tuple(a.shape)} and {tuple(b.shape)}")
+    return _lib.map_ops().block_sse(a, b, _map_shift(shift))
+
+
 class SqDiffFn(Function):
     """(a - b)^2 elementwise: nn.MSELoss(reduction='none')."""
 

@@ -5,20 +5,43 @@ forward(x) -> (x_tilde.detach(), losses) with losses =
 {z_entropy, y_entropy, bpp, total_loss, <distortion names>}; only
 total_loss carries grad."""
 import os
+from typing import NamedTuple, Optional
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from ... import _lib
 from ... import codec as _codec
 from ... import noise as _noise
-from ...functional import AbsFn, NonNegMultiFn, route_weight_gradients
+from ...functional import AbsFn, NonNegMultiFn, block_bits, block_sse, factorized, route_weight_gradients
 from ..blocks.entropy_model import symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
 from ..loss import get_loss_dict
 from .build import META_ARCH_REGISTRY
+
+
+class RDMap(NamedTuple):
+    """What `Compressor2018.rate_distortion_map` returns.  A block is 64 x 64 pixels (codec.MAP_BLOCK); the maps are
+    fp32 (N, Hb, Wb) over the padded size, Hb = ceil(h / 64), Wb = ceil(w / 64)."""
+    bits_y: torch.Tensor    # estimated bits of y's 4 x 4 positions of every block
+    bits_z: torch.Tensor    # estimated bits of z's position of every block
+    bits: torch.Tensor      # bits_y + bits_z, one fp32 addition
+    sse: torch.Tensor       # squared error of x against x_hat over the block's real pixels and 3 channels
+    pixels: np.ndarray      # (Hb, Wb) int64: the real pixels of every block
+    x_hat: torch.Tensor     # (N, 3, h, w), the eval forward's reconstruction (cropped when the image was padded)
+    p_y: Optional[torch.Tensor] = None   # with likelihoods=True: (N, M, H / 16, W / 16), what bits_y sums
+    p_z: Optional[torch.Tensor] = None   # (N, C_z, H / 64, W / 64), what bits_z sums
+
+
+def block_pixels(h, w):
+    """(ceil(h / 64), ceil(w / 64)) int64: how many pixels of an h x w image every 64 x 64 block holds."""
+    b = _codec.MAP_BLOCK
+    rows = np.minimum(b, h - b * np.arange(-(-h // b), dtype=np.int64))
+    cols = np.minimum(b, w - b * np.arange(-(-w // b), dtype=np.int64))
+    return rows[:, None] * cols[None, :]
 
 
 _SIDE = {}
@@ -424,6 +447,66 @@ class Compressor2018(nn.Module):
             for m, img in zip(idx, self._reconstruct_each(y_hat, hs)):
                 out[m] = img
         return out
+
+    # ---- rate and distortion maps: where the bits go and where the error is, block by block, from one eval pass
+    def _check_call(self, N, H, W, who):
+        """What a call on N images of padded size H x W needs of the model's settings (its arithmetic, its quality or
+        quality map), checked in front of any launch."""
+
+    def _begin_call(self, N, H, W, device, who):
+        """The state the gain hooks read during a call outside `forward`; `_end_call` drops it."""
+
+    def _end_call(self):
+        pass
+
+    def rate_distortion_map(self, x, likelihoods=False):
+        """The estimated bits and the squared error of every 64 x 64 pixel block (codec.MAP_BLOCK: one position of z,
+        4 x 4 of y -- the shape of a quality map) of x (N, 3, h, w), any h, w >= 1, from one eval pass with no coder
+        in the loop -> RDMap.
+
+        Eval mode only, under no_grad, on the current stream, always the serial route of the forward.  An image whose
+        size is no multiple of 64 is padded by the per-image streams' rule (edge replication) and its reconstruction
+        cropped and clamped as theirs is; at a multiple of 64 neither kernel runs and `x_hat` is `model(x)[0]` bit
+        for bit.  The quality is the forward's: `set_quality`, or the map of `set_quality_map` (checked against the
+        padded size in front of any launch).
+
+        This is an estimate of the eval forward, not of a stream: the bits are -log2 of the likelihoods the forward
+        scores (clamped as its loss clamps them), not a coder's output, and sigma (and the mean) come from the batch
+        as the forward computes them, not image by image as `compress_each` does."""
+        who = "rate_distortion_map"
+        if self.training:
+            raise RuntimeError(f"{who} runs in eval mode only: call model.eval() first")
+        if x.dim() != 4 or min(x.shape) < 1:
+            raise ValueError(f"{who}: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
+        N, _, h, w = x.shape
+        H, W = _codec.padded_size(h, w)
+        self._check_call(N, H, W, who)
+        self._clear_reparameterised()
+        y_shift, z_shift = ((_codec.MAP_BLOCK // d).bit_length() - 1 for d in (_codec.Y_DOWN, _codec.Z_DOWN))
+        em = self.entropy_model
+        with torch.no_grad():
+            xp = x
+            if (H, W) != (h, w):
+                _lib.require_device(x)
+                xp = _lib.stream_ops().pad_edge(x.contiguous(), H, W)
+            try:
+                self._begin_call(N, H, W, x.device, who)
+                y = self.analysis_transform(xp)
+                z = self._hyper_gain(self.prior_analysis(self._hyper_input(y)))
+                # the factorized model's (rint(z), p_z) without its loss: p_z in z's own logical shape
+                z_hat, p_z = factorized(z, em._cdf_estimator.flat_params(), False, None, em._cdf_estimator.dims, em.bin)
+                y_hat, p_y = self._forward_y(self._latent_gain(y), *self._prior(self._hyper_ungain(z_hat)))
+                if (H, W) == (h, w):
+                    x_hat = self._reconstruct(self._latent_ungain(y_hat))
+                else:
+                    x_hat = _lib.stream_ops().crop_clamp(self.synthesis_transform(self._latent_ungain(y_hat)), h, w)
+            finally:
+                self._end_call()
+            bits_y = block_bits(p_y, y_shift)
+            bits_z = block_bits(p_z, z_shift)
+            bits = block_bits(p_z, z_shift, add=bits_y)
+            sse = block_sse(x, x_hat, (_codec.MAP_BLOCK).bit_length() - 1)
+        return RDMap(bits_y, bits_z, bits, sse, block_pixels(h, w), x_hat, *((p_y, p_z) if likelihoods else ()))
 
     def _reconstruct_each(self, y_hat, hs):
         """[x_hat of image k, (1, 3, h_k, w_k)] from the latents of a group of streams that share one padded size, and

@@ -139,6 +139,16 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
         finally:
             self._gains = self._qualities = None   # no graph kept alive by module state
 
+    def _check_call(self, N, H, W, who):
+        super()._check_call(N, H, W, who)
+        self._one_quality(who)
+
+    def _begin_call(self, N, H, W, device, who):
+        self._use((self._one_quality(who),))
+
+    def _end_call(self):
+        self._gains = self._qualities = None
+
     def _hyper_gain(self, z):
         return channel_scale(z, self._gains[2])
 

@@ -73,6 +73,12 @@ class MeanScaleCompressor2018(Compressor2018):
         with torch.no_grad():
             return super().forward(x)
 
+    def _check_call(self, N, H, W, who):
+        cm = self.conditional_model
+        if float(cm.bin) != 1.0:
+            raise NotImplementedError(f"{who} rounds the residual to integers, as the eval forward does: BIN must be 1, "
+                                      f"got {cm.bin}")
+
     def _forward_y(self, y, sigma, mu):
         cm = self.conditional_model
         if self.training:

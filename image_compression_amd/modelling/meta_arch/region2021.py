@@ -142,6 +142,16 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
         finally:
             self._clear()   # no graph kept alive by module state
 
+    def _check_call(self, N, H, W, who):
+        super()._check_call(N, H, W, who)   # one quality, or a map
+        self._call_map(N, H, W, who)
+
+    def _begin_call(self, N, H, W, device, who):
+        self._use_map(self._call_map(N, H, W, who), device)
+
+    def _end_call(self):
+        self._clear()
+
     def _hyper_gain(self, z):
         return block_scale(z, self._gains[2], self._idx, 0)
 

@@ -661,6 +661,25 @@ int ic_block_mse_bwd(const float* a, const float* b, const float* w, int R, cons
                      int N, int C, int H, int W, long long sn, long long sc, long long sh, long long sw, float* ga,
                      float* gb, void* stream);
 
+/* ---- rate and distortion maps (additive to version 4; inference only).  One value per block of 2^shift x 2^shift
+ *      positions of every image: out (N, ceil(H / 2^shift), ceil(W / 2^shift)) dense; the blocks of the last row and
+ *      column may be partial.  A tensor is the logical (N, C, H, W) with element strides; inside an image its storage
+ *      is dense channels-last (sc 1, sw C, sh W C) or dense NCHW (sw 1, sh W, sc H W), the stride of an extent of 1 is
+ *      not looked at, sn >= 0 is free.  IC_ERR_ARG before any launch for a null pointer, another layout, N outside
+ *      1 .. 65535, an extent below 1, C H W >= 2^31 or a shift outside 0 .. 6.  One launch each; neither allocates or
+ *      waits for its stream; no atomics.  The order of every sum is a function of (C, H, W, shift, layout) alone:
+ *      image n's map has the same bits whatever N, n, the pointers' alignment (16-byte loads are used where an
+ *      address allows them and change no bit) and the run. ---- */
+/* out[n,bi,bj] = the sum over the block and all channels of clamp(-log2(p + 1e-10), 0, 50), the term of
+ * ic_ce_loss_fwd; with `add` (the shape of out; NULL for none) out = add + that sum, one fp32 addition */
+int ic_block_bits(const float* p, int N, int C, int Hm, int Wm, long long sn, long long sc, long long sh, long long sw,
+                  int shift, const float* add, float* out, void* stream);
+/* out[n,bi,bj] = the sum over the block and all channels of (a - b)^2, every operation rounded once; a is walked
+ * along its storage, b at its own strides (an, ...) / (bn, ...) */
+int ic_block_sse(const float* a, const float* b, int N, int C, int H, int W, long long an, long long ac, long long ah,
+                 long long aw, long long bn, long long bc, long long bh, long long bw, int shift, float* out,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -30,6 +30,11 @@ tables: the eval forward, compress and decompress at 1 x --height x --width; ic_
 ic_channel_scale / _bwd with a row per image and ic_block_mse beside ic_mse by device events on N images; one eager
 training step of both at 32 x 256 x 256; and the coded bytes of three maps.
 
+--rdmap N times the rate and distortion maps: ic_block_bits beside ic_ce_loss_fwd on the p_y and the p_z of N images
+and ic_block_sse beside ic_mse_fwd on the images and their reconstructions, by device events over 20 back-to-back
+calls; `rate_distortion_map` beside the eval forward at 1 x --height x --width on the gained and the region model;
+and per image the estimated bytes (bits.sum() / 8) beside the bytes of its `compress_each` stream.
+
 --context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
 --each works on it too (its loop arm is then the fused model's own compress / decompress).
 
@@ -205,9 +210,15 @@ def main():
     ap.add_argument("--region", type=int, default=0, metavar="N",
                     help="GainedMeanScaleCompressor2018 and RegionGainedMeanScaleCompressor2018 alternately; kernels on "
                          "the y of N images")
+    ap.add_argument("--rdmap", type=int, default=0, metavar="N",
+                    help="the rate / distortion map kernels beside ic_ce_loss_fwd / ic_mse_fwd on N images; "
+                         "rate_distortion_map beside the eval forward")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.rdmap:
+        _emit(rdmap_bench(args), args.out)
+        return
     if args.region:
         _emit(region_bench(args), args.out)
         return
@@ -686,6 +697,91 @@ def region_bench(args):
     for a, v in t.items():
         out[f"{a}_train_step_32x256x256_ms"] = round(min(v), 3)
         out[f"{a}_train_step_32x256x256_all_ms"] = [round(u, 3) for u in v]
+    return out
+
+
+def rdmap_bench(args):
+    """--rdmap N: the map kernels beside the reductions that read the same bytes, by device events on the likelihoods
+    and images of N images; rate_distortion_map beside the eval forward at one image on the gained and the region
+    model; and per image the estimated bytes beside the bytes of its stream.  Candidates alternate inside every
+    repetition."""
+    from image_compression_amd import _lib, codec
+    from image_compression_amd import functional as F
+    archs = ("GainedMeanScaleCompressor2018", "RegionGainedMeanScaleCompressor2018")
+    GAINED, REGION = archs
+    H, W, reps, N = args.height, args.width, args.reps, args.rdmap
+    hb, wb = -(-H // 64), -(-W // 64)
+    g = torch.Generator(device="cuda").manual_seed(5)
+    out = {"metric": f"rate / distortion maps at {N} x 3 x {H} x {W} (kernels) and 1 x 3 x {H} x {W} (model), weight "
+                     f"cache, best of {reps} alternating reps", "unit": "ms", "reps": reps, "weight_scale": args.scale,
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0), "
+                   "ladder tables +-0.3 per level"}
+    x = torch.rand(1, 3, H, W, device="cuda", generator=g)
+    xn = torch.rand(N, 3, H, W, device="cuda", generator=g)
+    with torch.no_grad(), F.weight_cache():
+        models = {a: _build(a, args.scale)[0] for a in archs}
+        for m in models.values():
+            for name, sign in (("log_y", 1.0), ("log_inv_y", -1.0), ("log_z", 1.0), ("log_inv_z", -1.0)):
+                getattr(m.gain, name).copy_(sign * 0.3 * torch.arange(m.levels, device="cuda").view(-1, 1))
+        models[GAINED].set_quality(3.0)
+        models[REGION].set_quality_map(codec.block_map(64 * hb, 64 * wb, 6, 1, [(64 * (hb // 4), 64 * (wb // 4),
+                                                                                 64 * (hb // 2), 64 * (wb // 2), 5)]))
+        # the model: rate_distortion_map beside the eval forward
+        fns = {"forward": lambda m: m(x), "rate_distortion_map": lambda m: m.rate_distortion_map(x)}
+        for m in models.values():
+            for fn in fns.values():
+                for _ in range(2):
+                    fn(m)
+        t = {(k, a): [] for k in fns for a in archs}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                for a, m in models.items():
+                    t[k, a].append(_wall(lambda: fn(m), 1))
+        for (k, a), v in t.items():
+            out[f"{a}_{k}_ms"] = round(min(v), 4)
+            out[f"{a}_{k}_all_ms"] = [round(u, 3) for u in v]
+        for a in archs:
+            out[f"{a}_map_minus_forward_ms"] = round(min(t["rate_distortion_map", a]) - min(t["forward", a]), 4)
+        # the kernels by device events
+        m = models[GAINED]
+        rd = m.rate_distortion_map(xn, likelihoods=True)
+        mops, ops = _lib.map_ops(), _lib.ops()
+        p_y, p_z, xh = rd.p_y, rd.p_z, rd.x_hat.contiguous()
+        calls = 20
+        kern = {   # name: (the call, bytes the kernel must move)
+            "ce_loss_fwd_y": (lambda: ops.ce_loss_fwd(p_y), 4 * p_y.numel()),
+            "block_bits_y": (lambda: mops.block_bits(p_y, 2), 4 * p_y.numel()),
+            "ce_loss_fwd_z": (lambda: ops.ce_loss_fwd(p_z), 4 * p_z.numel()),
+            "block_bits_z": (lambda: mops.block_bits(p_z, 0), 4 * p_z.numel()),
+            "block_bits_z_add": (lambda: mops.block_bits(p_z, 0, rd.bits_y), 4 * p_z.numel()),
+            "mse_fwd": (lambda: ops.mse_fwd(xn, xh), 8 * xn.numel()),
+            "block_sse": (lambda: mops.block_sse(xn, xh, 6), 8 * xn.numel()),
+            "block_sse_as_the_model_calls_it": (lambda: mops.block_sse(xn, rd.x_hat, 6), 8 * xn.numel()),
+        }
+        for fn, _ in kern.values():
+            fn()
+        tk = {k: [] for k in kern}
+        for _ in range(reps):
+            for k, (fn, _) in kern.items():
+                tk[k].append(_events(lambda: [fn() for _ in range(calls)], 1) / calls)
+        out["kernels_ms_per_call"] = {k: round(min(v), 5) for k, v in tk.items()}
+        out["kernels_all_ms_per_call"] = {k: [round(u, 5) for u in v] for k, v in tk.items()}
+        out["kernels_bytes"] = {k: b for k, (_, b) in kern.items()}
+        out["kernels_gb_per_s"] = {k: round(kern[k][1] / min(v) / 1e6, 1) for k, v in tk.items()}
+        out["kernels_shapes"] = {"p_y": list(p_y.shape), "p_y_strides": list(p_y.stride()), "p_z": list(p_z.shape),
+                                 "p_z_strides": list(p_z.stride()), "x_hat_strides": list(rd.x_hat.stride())}
+        out["kernels_calls_between_events"] = calls
+        for new, old in (("block_bits_y", "ce_loss_fwd_y"), ("block_bits_z", "ce_loss_fwd_z"), ("block_sse", "mse_fwd")):
+            ratio = min(tk[new]) / min(tk[old])
+            out[f"{new}_over_{old}"], out[f"{new}_within_1.25x"] = round(ratio, 3), bool(ratio <= 1.25)
+        # per image: the estimate beside the stream (a table, not a claim: no trained weights)
+        table = []
+        for a, m in models.items():
+            rd, streams = m.rate_distortion_map(xn), m.compress_each(xn)
+            bits = rd.bits.double().sum(dim=(1, 2)).cpu().tolist()
+            table += [{"arch": a, "image": n, "estimated_bytes": round(bits[n] / 8, 1), "stream_bytes": len(streams[n]),
+                       "stream_minus_estimate": round(len(streams[n]) - bits[n] / 8, 1)} for n in range(N)]
+        out["bytes_table"] = table
     return out
 
 
