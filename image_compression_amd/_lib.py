@@ -242,6 +242,12 @@ SIGNATURES = {
     "ic_block_bits": (c_int, [c_void, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_int, c_void, c_void, c_void]),
     "ic_block_sse": (c_int, [c_void, c_void, c_int, c_int, c_int, c_int, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll, c_ll,
                              c_int, c_void, c_void]),
+    # coding to a byte budget: chunk lengths without the bytes, y's symbols of many candidates (additive to
+    # ic_version 4)
+    "ic_codec_measure_seg": (c_int, [c_void, c_int, c_ll, c_void, c_int, c_void, c_size, c_int, P(c_int), P(c_ll),
+                                     c_void, c_int, c_void, c_void]),
+    "ic_gain_symbolize_seg": (c_int, [c_void, c_ll, c_ll, c_int, c_void, c_void, c_int, P(c_int), c_void, c_void,
+                                      c_void, P(c_int), c_void]),
 }
 
 _lib = None
@@ -266,6 +272,7 @@ ckbd_ops = _namespace("imgcomp_ckbd", "the checkerboard context model's masks, p
 gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel scaling")
 region_ops = _namespace("imgcomp_region", "scaling by a gain row per block and the block-weighted squared error")
 map_ops = _namespace("imgcomp_map", "the estimated bits and the squared error of every block")
+rate_ops = _namespace("imgcomp_rate", "the sizes and the symbols of candidate streams, for coding to a byte budget")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

@@ -155,6 +155,23 @@ the tables, rows, chunks and payloads are those of the gained streams with the g
 The conditional kind is 2 or 3.  S >= 2, map_h == H/64 and map_w == W/64, and the buffer holds the whole map, or the
 parser raises ValueError; a model with another S refuses the stream.  The decoder takes the map from the stream.
 The eight containers do not read one another: every parser raises ValueError on another's magic.
+
+Coding to a byte budget (`GainedMeanScaleCompressor2018.compress_each_to`): the search rule
+--------------------------------------------------------------------------------------------
+A budget B is a bound on len() of one image's "ICRQ" stream, header included.  The size of a candidate quality is
+measured, never estimated: `image_stream_bytes` of the chunk lengths the coder itself reports for that candidate.
+Sizes are not assumed monotone in the quality (the gain tables are learnt), so the search is a grid search in
+`rounds` rounds of `candidates` = Q qualities, per image:
+    round 1 searches `budget_grid(S, Q)`: float32(k (S-1) / (Q-1)), k = 0 .. Q-1, the quotient in float64;
+    a round's choice is `budget_choice`: the largest of its candidates whose size is <= B (the largest that fits,
+        not the one before the first that fails);
+    every later round searches `budget_refine(chosen, next, Q)`: float32(lo + j (hi - lo) / (Q+1)), j = 1 .. Q, in
+        float64, of which only the values strictly inside (lo, hi) are kept, once each, ascending; `next` is
+        `budget_next`: the next larger quality among everything measured for the image so far.  `chosen` stays when
+        none of them fits;
+    an image whose choice is S-1 has no later round; nor has one for which no candidate of round 1 fits: that is a
+        `BudgetError` (strict), or the image is coded at quality 0 and is the one stream that may exceed its budget.
+The result is optimal relative to the qualities measured, not to the interval.
 """
 import math
 import struct
@@ -607,6 +624,57 @@ def parse_gained_image(data, abi, compute_dtype):
     checks of `parse_image`, and those of the levels and the quality.  Nothing is launched here."""
     return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION,
                   GainedImageHeader, _check_gained_image_header)
+
+
+# ---- coding to a byte budget: the search rule of `compress_each_to` (the docstring's last section)
+class BudgetError(ValueError):
+    """No candidate of the first round fits an image's budget: `image` (its index in the call), `budget` (bytes)
+    and `smallest` (the smallest stream measured for it, bytes)."""
+
+    def __init__(self, image, budget, smallest):
+        super().__init__(f"codec: image {image} does not fit {budget} bytes at any quality searched: its smallest "
+                         f"stream is {smallest} bytes")
+        self.image, self.budget, self.smallest = int(image), int(budget), int(smallest)
+
+
+def _check_candidates(Q, least):
+    if isinstance(Q, bool) or not isinstance(Q, (int, np.integer)) or Q < least:
+        raise ValueError(f"codec: the number of candidates is an integer >= {least}, got {Q!r}")
+    return int(Q)
+
+
+def budget_grid(S, Q):
+    """The Q >= 2 qualities of round 1 for a model with S levels, ascending: 0 and S-1 exactly at the ends."""
+    S, Q = _check_levels(S), _check_candidates(Q, 2)
+    return [float(np.float32(k * (S - 1) / (Q - 1))) for k in range(Q)]
+
+
+def budget_refine(lo, hi, Q):
+    """Up to Q qualities strictly inside (lo, hi), ascending and distinct: the float32 values of lo + j (hi - lo) /
+    (Q + 1), j = 1 .. Q, that are neither end.  Empty when no float32 lies between the two."""
+    Q, lo, hi = _check_candidates(Q, 1), float(lo), float(hi)
+    if not lo <= hi:     # NaN included
+        raise ValueError(f"codec: no interval ({lo!r}, {hi!r}) to refine")
+    qs = {float(np.float32(lo + j * (hi - lo) / (Q + 1))) for j in range(1, Q + 1)}
+    return sorted(q for q in qs if lo < q < hi)
+
+
+def budget_choice(qualities, sizes, budget):
+    """The largest of `qualities` whose entry of `sizes` is <= budget, or None when none is."""
+    fit = [q for q, n in zip(qualities, sizes) if n <= budget]
+    return max(fit) if fit else None
+
+
+def budget_next(measured, chosen):
+    """The next larger quality than `chosen` among `measured`, or None."""
+    above = [q for q in measured if q > chosen]
+    return min(above) if above else None
+
+
+def image_stream_bytes(fixed, *lens):
+    """len() of a per-image stream whose `*_image_fixed_bytes` is `fixed` and whose chunk-length tables are `lens`:
+    the fixed part counts every chunk's 256 bytes of lane states, the lengths count them again."""
+    return int(fixed) + sum(int(np.asarray(l, dtype=np.int64).sum()) - CHUNK_HEAD * len(l) for l in lens)
 
 
 # ---- region containers "ICRM" (batch) and "ICRR" (per image): the gained streams with a quality per 64 x 64 block

@@ -170,7 +170,9 @@ __device__ __forceinline__ int row_of(const CodecArgs& a, long long g) {
 // ascending lane; the 64 final states go in front.  slot = 2*64*R + 256 bytes is the worst case (one
 // word per symbol).  *length = bytes used; they end at the slot's end.
 // The chunk holds the nc symbols from global index c0 on; a.cdf is the table of those symbols.
-template <bool LDS>
+// STORE = false is the coder without its output (ic_codec_measure_seg): the same steps -- state update, ballot of
+// the emitting lanes, popcount -- and the same *length, with no store to the slot, which may then be null.
+template <bool LDS, bool STORE = true>
 __device__ __forceinline__ void encode_chunk(const int* __restrict__ sym, const CodecArgs& a, long long c0, int nc,
                                              unsigned short* __restrict__ slot, uint32_t* __restrict__ length,
                                              uint32_t* lds) {
@@ -197,15 +199,17 @@ __device__ __forceinline__ void encode_chunk(const int* __restrict__ sym, const 
     const unsigned long long mask = __ballot(emit);
     const int cnt = __popcll(mask);
     if (emit) {
-      slot[ptr - cnt + __popcll(mask & below)] = (unsigned short)(x & 0xffffu);
+      if (STORE) slot[ptr - cnt + __popcll(mask & below)] = (unsigned short)(x & 0xffffu);
       x >>= 16;
     }
     ptr -= cnt;
     if (active) x = ((x / freq) << 16) + (x % freq) + start;
   }
   ptr -= 128;
-  slot[ptr + 2 * lane] = (unsigned short)(x & 0xffffu);
-  slot[ptr + 2 * lane + 1] = (unsigned short)(x >> 16);
+  if (STORE) {
+    slot[ptr + 2 * lane] = (unsigned short)(x & 0xffffu);
+    slot[ptr + 2 * lane + 1] = (unsigned short)(x >> 16);
+  }
   if (lane == 0) *length = (uint32_t)((slot_words - (size_t)ptr) * 2);
 }
 
@@ -255,6 +259,19 @@ __global__ void __launch_bounds__(64) codec_encode_seg_k(const int* __restrict__
     encode_chunk<true>(sym, a, c0, nc, slot, lengths + blockIdx.x, lds);
   else
     encode_chunk<false>(sym, a, c0, nc, slot, lengths + blockIdx.x, lds);
+}
+
+// codec_encode_seg_k without its output: lengths[segment * cps + chunk] alone, by the same device function
+__global__ void __launch_bounds__(64) codec_measure_seg_k(const int* __restrict__ sym, SegArgs s,
+                                                          uint32_t* __restrict__ lengths) {
+  extern __shared__ uint32_t lds[];
+  long long c0;
+  int nc;
+  const CodecArgs a = seg_chunk(s, &c0, &nc);
+  if (table_bytes(a.nrows, a.K) <= CODEC_LDS_BYTES)
+    encode_chunk<true, false>(sym, a, c0, nc, nullptr, lengths + blockIdx.x, lds);
+  else
+    encode_chunk<false, false>(sym, a, c0, nc, nullptr, lengths + blockIdx.x, lds);
 }
 
 // out = [lengths: nchunks x u32][chunk 0 bytes][chunk 1 bytes]...; block = chunk; its offset is the
@@ -564,6 +581,24 @@ int ic_codec_encode_seg(const int* sym, int nseg, long long seg_len, const unsig
   const SegArgs a{seg_len, rows, C, pool, seg_dev, nrows, steps_per_chunk, cps};
   hipLaunchKernelGGL(codec_encode_seg_k, dim3((unsigned)(cps * nseg)), dim3(64), lds, st, sym, a, (unsigned short*)ws,
                      lengths);
+  IC_CHECK_LAUNCH();
+  return IC_OK;
+}
+
+int ic_codec_measure_seg(const int* sym, int nseg, long long seg_len, const unsigned char* rows, int C,
+                         const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                         const long long* seg_off, int* seg_dev, int steps_per_chunk, unsigned int* lengths,
+                         void* stream) {
+  size_t lds = 0;   // the dynamic LDS of the encode launch: the largest table that is staged
+  if (!sym || !pool || !seg_dev || !lengths ||
+      !codec_seg_ok(nseg, seg_len, rows, C, pool_words, nrows, seg_k, seg_off, steps_per_chunk, &lds))
+    return IC_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t e = seg_upload(nseg, seg_k, seg_off, seg_dev, st);
+  if (e != hipSuccess) return (int)e;
+  const int cps = (int)ic_codec_chunks(seg_len, steps_per_chunk);
+  const SegArgs a{seg_len, rows, C, pool, seg_dev, nrows, steps_per_chunk, cps};
+  hipLaunchKernelGGL(codec_measure_seg_k, dim3((unsigned)(cps * nseg)), dim3(64), lds, st, sym, a, lengths);
   IC_CHECK_LAUNCH();
   return IC_OK;
 }

@@ -1870,6 +1870,84 @@ Tensor map_block_sse_meta(const Tensor& a, const Tensor& b, int64_t shift) {
   return new_map(a, shift);
 }
 
+// ---------------------------------------------------------------- coding to a byte budget (imgcomp_rate)
+// stream_encode_seg without its bytes: the chunk lengths, int32 (nseg * chunks per segment) on the device
+Tensor rate_measure_seg(const Tensor& sym, int64_t nseg, const std::optional<Tensor>& rows, int64_t C, const Tensor& pool,
+                        int64_t nrows, at::IntArrayRef seg_k, at::IntArrayRef seg_off, int64_t steps) {
+  check_codec(sym, at::kInt, "sym");
+  check_codec(pool, at::kInt, "table pool");
+  const SegTables t = seg_tables(nseg, seg_k, seg_off);
+  const int64_t n = sym.numel();
+  TORCH_CHECK(n > 0 && n % nseg == 0, "imgcomp_rate: ", n, " symbols do not make ", nseg, " equal segments");
+  const unsigned char* rp = codec_rows(rows, n);
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR, "imgcomp_rate: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  const int64_t seg_len = n / nseg, chunks = ic_codec_seg_chunks((int)nseg, seg_len, (int)steps);
+  TORCH_CHECK(chunks > 0, "imgcomp_rate: too many chunks");
+  Tensor lens = at::empty({chunks}, sym.options());
+  Tensor kt = at::empty({2 * nseg}, sym.options());
+  check_rc(ic_codec_measure_seg(sym.data_ptr<int>(), (int)nseg, seg_len, rp, (int)C,
+                                (const unsigned int*)pool.data_ptr<int>(), (size_t)pool.numel(), (int)nrows, t.k.data(),
+                                t.off.data(), kt.data_ptr<int>(), (int)steps, (unsigned int*)lens.data_ptr<int>(),
+                                stream_of(sym)),
+           "codec_measure_seg");
+  return lens;
+}
+
+// y (N, *, C) contiguous, read in place; g (M, C); mu: the M candidates' means back to back, each an image of y's
+// size; img: the image of every candidate
+void check_rate_shapes(const Tensor& y, const Tensor& g, const Tensor& mu, at::IntArrayRef img) {
+  const int64_t M = (int64_t)img.size();
+  TORCH_CHECK(y.dim() >= 2 && y.numel() > 0, "imgcomp_rate: y must be a non-empty (N, *, C) tensor, got ", y.sizes());
+  TORCH_CHECK(M >= 1 && M <= 65535 && g.dim() == 2 && g.size(0) == M && g.size(1) == y.size(-1),
+              "imgcomp_rate: the gains ", g.sizes(), " must be (", M, " candidates, ", y.size(-1), ")");
+  TORCH_CHECK(mu.numel() == M * (y.numel() / y.size(0)), "imgcomp_rate: mu (", mu.numel(), " values) must hold ", M,
+              " images of ", y.numel() / y.size(0), " values");
+}
+
+std::tuple<Tensor, std::vector<int64_t>> rate_gain_symbolize_seg(const Tensor& y, const Tensor& g, const Tensor& mu,
+                                                                 at::IntArrayRef img) {
+  check_operand(y, "y");
+  check_operand(g, "g");
+  check_operand(mu, "mu");
+  check_rate_shapes(y, g, mu, img);
+  TORCH_CHECK(y.is_contiguous() && g.is_contiguous() && mu.is_contiguous(), "imgcomp_rate: y, g and mu must be contiguous");
+  TORCH_CHECK(y.device() == g.device() && y.device() == mu.device(), "imgcomp_rate: y, g and mu must be on one device");
+  const int64_t M = (int64_t)img.size(), N = y.size(0), C = y.size(-1);
+  TORCH_CHECK(N <= 65535 && C <= INT_MAX, "imgcomp_rate: y is too large: ", y.sizes());
+  std::vector<int> im;
+  for (int64_t m = 0; m < M; ++m) {
+    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_rate: candidate ", m, " names image ", img[m], " of ", N);
+    im.push_back((int)img[m]);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor sym = symbols_out(mu);
+  Tensor kd = at::empty({2 * M}, y.options().dtype(at::kInt));   // the maxima, then the images
+  std::vector<int> kmax((size_t)M, 0);
+  const int rc = ic_gain_symbolize_seg(y.data_ptr<float>(), N, y.numel() / N / C, (int)C, g.data_ptr<float>(),
+                                       mu.data_ptr<float>(), (int)M, im.data(), kd.data_ptr<int>() + M, sym.data_ptr<int>(),
+                                       kd.data_ptr<int>(), kmax.data(), stream_of(y));
+  if (rc == IC_ERR_ARG)
+    for (int64_t m = 0; m < M; ++m)
+      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_rate: candidate ", m, " (image ", img[m],
+                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "gain_symbolize_seg");
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
+Tensor rate_measure_seg_meta(const Tensor& sym, int64_t nseg, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t,
+                             at::IntArrayRef, at::IntArrayRef, int64_t steps) {
+  TORCH_CHECK(nseg >= 1 && sym.numel() % nseg == 0, "imgcomp_rate: symbols do not make equal segments");
+  const int64_t chunks = ic_codec_seg_chunks((int)nseg, sym.numel() / nseg, (int)steps);
+  TORCH_CHECK(chunks > 0, "imgcomp_rate: bad symbol count or steps_per_chunk");
+  return at::empty({chunks}, sym.options().dtype(at::kInt));
+}
+std::tuple<Tensor, std::vector<int64_t>> rate_gain_symbolize_seg_meta(const Tensor& y, const Tensor& g, const Tensor& mu,
+                                                                      at::IntArrayRef img) {
+  check_rate_shapes(y, g, mu, img);
+  return {symbols_out(mu), std::vector<int64_t>(img.size(), 0)};
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -2237,4 +2315,22 @@ TORCH_LIBRARY_IMPL(imgcomp_map, CUDA, m) {
 TORCH_LIBRARY_IMPL(imgcomp_map, Meta, m) {
   m.impl("block_bits", map_block_bits_meta);
   m.impl("block_sse", map_block_sse_meta);
+}
+
+// Coding to a byte budget (GainedMeanScaleCompressor2018.compress_each_to): additive, in a namespace of its own.
+// Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_rate, m) {
+  m.def("measure_seg(Tensor sym, int nseg, Tensor? rows, int channels, Tensor pool, int nrows, int[] seg_k, "
+        "int[] seg_off, int steps_per_chunk) -> Tensor");
+  m.def("gain_symbolize_seg(Tensor y, Tensor g, Tensor mu, int[] img) -> (Tensor, int[])");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_rate, CUDA, m) {
+  m.impl("measure_seg", rate_measure_seg);
+  m.impl("gain_symbolize_seg", rate_gain_symbolize_seg);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_rate, Meta, m) {
+  m.impl("measure_seg", rate_measure_seg_meta);
+  m.impl("gain_symbolize_seg", rate_gain_symbolize_seg_meta);
 }

@@ -976,6 +976,42 @@ def channel_scale(x, g):
     return ChannelScaleFn.apply(x, g)
 
 
+# ============================================================== coding to a byte budget
+def _on_device(who, **operands):
+    for what, t in operands.items():
+        if t is not None and not t.is_cuda:
+            raise RuntimeError(f"imgcomp: HIP kernels need tensors on a ROCm (cuda) device; {who} got {what} on {t.device}")
+
+
+def measure_seg(sym, nseg, rows, channels, pool, nrows, seg_k, seg_off, steps_per_chunk):
+    """The chunk lengths the segmented coder reports for these symbols and tables, int32 (nseg * chunks per segment)
+    on the device, without coding a byte: the operands of torch.ops.imgcomp_stream.encode_seg
+    (torch.ops.imgcomp_rate.measure_seg).  Inference only."""
+    _on_device("measure_seg", sym=sym, rows=rows, pool=pool)
+    return _lib.rate_ops().measure_seg(sym, int(nseg), rows, int(channels), pool, int(nrows), [int(k) for k in seg_k],
+                                       [int(o) for o in seg_off], int(steps_per_chunk))
+
+
+def gain_symbolize_seg(y, g, mean, img):
+    """The symbols of y (N, C, *) for M candidates: candidate m is image img[m] scaled by the gain row g[m] of g
+    (M, C) and coded about mean[m] of mean (M, C, *) -> (int32 rint(y[img[m]] * g[m] - mean[m]) of the M candidates
+    back to back, each in (*, c) order, [kmax of candidate m]).  Bit for bit `channel_scale` then
+    `symbolize_mean_seg` on the gathered batch y[img], which is never formed
+    (torch.ops.imgcomp_rate.gain_symbolize_seg).  Inference only; ValueError naming the candidate whose symbols
+    exceed the coder's limit."""
+    _lib.require_device(y, g, mean)
+    img = [int(i) for i in img]
+    if y.dim() < 2 or g.dim() != 2 or tuple(g.shape) != (len(img), y.shape[1]):
+        raise ValueError(f"the gains {tuple(g.shape)} must be ({len(img)} candidates, C) for a tensor of shape "
+                         f"{tuple(y.shape)}")
+    if tuple(mean.shape) != (len(img), *y.shape[1:]):
+        raise ValueError(f"the mean {tuple(mean.shape)} must hold {len(img)} candidates of shape {tuple(y.shape[1:])}")
+    _inference_only("gain_symbolize_seg", y=y, g=g, mean=mean)
+    sym, kmax = _lib.rate_ops().gain_symbolize_seg(_to_last(y.detach()), g.detach().contiguous(), _to_last(mean.detach()),
+                                                   img)
+    return sym, [int(k) for k in kmax]
+
+
 # ============================================================== region-of-interest coding
 def _block_map(idx, device):
     """A block map as the kernels take it: contiguous uint8 on the device."""

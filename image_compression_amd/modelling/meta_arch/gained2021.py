@@ -22,7 +22,11 @@ from the stream, never from the model.  In training mode with `sample_quality` (
 an integer level uniformly from a CPU generator seeded with cfg.SEED (`last_quality`; no device draw, the Philox
 order z, then y is unchanged); with `sample_quality = False` it uses `quality`.  The distortion weight of a step is
 LOSS_WEIGHTS at its level, between levels exp of the interpolated logarithms: it and the level change on the host
-every step, which is why TrainStep(graph=True) refuses this model (`graph_refusal`)."""
+every step, which is why TrainStep(graph=True) refuses this model (`graph_refusal`).
+
+Budget.  `compress_each_to(x, budgets)` chooses the quality of every image so that its stream holds at most its
+budget of bytes: the grid search of codec.py on sizes the coder itself reports, every candidate of every image
+measured from one pass of g_a and h_a.  It neither reads nor changes `quality`."""
 import math
 from numbers import Real
 
@@ -192,3 +196,134 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
 
     def _begin_decode(self, headers):
         self._use([h.quality for h in headers])
+
+    # ---- coding to a byte budget: the search rule of codec.py on sizes the coder itself reports
+    def _check_budget_call(self, x, budgets, steps_per_chunk, candidates, rounds):
+        """The budgets of a `compress_each_to` call, one int per image; every check in front of any launch."""
+        who = "compress_each_to"
+        if x.dim() != 4 or min(x.shape) < 1:
+            raise ValueError(f"{who}: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
+        N = x.shape[0]
+
+        def integer(v):
+            return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
+
+        if integer(budgets):
+            budgets = [budgets] * N
+        elif isinstance(budgets, (list, tuple, np.ndarray)) and getattr(budgets, "ndim", 1) == 1:
+            budgets = list(budgets)
+        else:
+            raise ValueError(f"{who}: budgets are one positive int or a sequence of them, got {budgets!r}")
+        if len(budgets) != N:
+            raise ValueError(f"{who}: {len(budgets)} budgets for {N} images")
+        if not all(integer(b) and b > 0 for b in budgets):
+            raise ValueError(f"{who}: a budget is a positive int, a number of bytes, got {budgets!r}")
+        for name, v, lo, hi in (("candidates", candidates, 2, 64), ("rounds", rounds, 1, 4),
+                                ("steps_per_chunk", steps_per_chunk, 1, _codec.MAX_STEPS)):
+            if not integer(v) or not lo <= v <= hi:
+                raise ValueError(f"{who}: {name} is an integer in [{lo}, {hi}], got {v!r}")
+        if N * candidates > 65535:
+            raise ValueError(f"{who}: {N} images x {candidates} candidates exceed the 65535 segments of one launch")
+        return [int(b) for b in budgets]
+
+    @torch.no_grad()
+    def compress_each_to(self, x, budgets, steps_per_chunk=1024, candidates=8, rounds=2, strict=True):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1, and `budgets` (one positive int, or N of them: bytes of the whole
+        stream, header included) -> (a list of N "ICRQ" streams as `compress_each` writes them, their float32
+        qualities): every image at the quality the search rule of codec.py chooses for its budget among `rounds`
+        rounds of `candidates` qualities, so that len(stream) <= budget.  `model.quality` is not looked at and not
+        changed.
+
+        All candidates of all images are measured by one set of launches per round, from one pass of g_a and h_a:
+        the gains, the symbols of z and of y, h_s (image by image, as `compress_each` and the decoder run it, which
+        is what makes the measured size the size of the stream), the table rows and the coder's own chunk lengths
+        (`measure_seg`: the coder without its output); one small copy of the lengths comes back per round.  Only the
+        N chosen candidates are coded.
+
+        An image that fits at no quality of round 1: codec.BudgetError (a ValueError with .image, .budget,
+        .smallest) in front of any packing; with strict=False it is coded at quality 0 and is the one stream that may
+        exceed its budget."""
+        from ...functional import gain_symbolize_seg, measure_seg
+        from ..blocks.entropy_model import symbolize_seg, symbols_as_tensor, table_pool
+        who = "compress_each_to"
+        budgets = self._check_budget_call(x, budgets, steps_per_chunk, candidates, rounds)
+        self._codable_each()
+        em, cm, R = self.entropy_model, self.conditional_model, int(steps_per_chunk)
+        x, (N, h, w, H, W) = self._pad_each(x)
+        y = self.analysis_transform(x)
+        z = self.prior_analysis(self._hyper_input(y))
+        z_tables, y_tables = {}, {}     # one table per K and tensor kind for the whole call
+
+        def tables_z(K):
+            if K not in z_tables:
+                z_tables[K] = em.tables(K)
+            return z_tables[K]
+
+        def tables_y(K):
+            if K not in y_tables:
+                y_tables[K] = cm.tables(K, y.device)
+            return y_tables[K]
+
+        measured = [{} for _ in range(N)]   # quality -> bytes, everything measured for the image so far
+        chosen = [None] * N                 # quality -> what the final coding needs of that candidate
+        kept = [None] * N
+        todo = {n: _codec.budget_grid(self.levels, candidates) for n in range(N)}
+        try:
+            for rnd in range(rounds):
+                cands = [(n, q) for n in sorted(todo) for q in todo[n]]
+                if not cands:
+                    break
+                img, qs = [n for n, _ in cands], [q for _, q in cands]
+                M = len(cands)
+                self._use(qs)
+                g_y, _, g_z, g_inv_z = self._gains
+                try:
+                    z_sym, kz = symbolize_seg(channel_scale(z[torch.as_tensor(img, device=z.device)], g_z))
+                    z_hat = channel_scale(symbols_as_tensor(z_sym.to(torch.float32), (M, *z.shape[1:])), g_inv_z)
+                    sigma, mean = self._prior_each(z_hat)
+                    y_sym, ky = gain_symbolize_seg(y, g_y, mean, img)
+                except ValueError as e:
+                    raise ValueError(f"{who}: among the candidates {cands}: {e}") from None
+                rows = cm.scale_rows(sigma.expand_as(mean))
+                lz = measure_seg(z_sym, M, None, em.channels, *table_pool(tables_z, kz), R)
+                ly = measure_seg(y_sym, M, rows, 0, *table_pool(tables_y, ky), R)
+                lens = torch.cat([lz, ly]).cpu().numpy().astype(np.int64)    # the one D2H copy of the round
+                lz, ly = lens[:lz.numel()].reshape(M, -1), lens[lz.numel():].reshape(M, -1)
+                fixed = _codec.gained_image_fixed_bytes(self._header(1, H, W, y, z, R, 0, 0, (h, w)))
+                size = [_codec.image_stream_bytes(fixed, lz[m], ly[m]) for m in range(M)]
+                nz, ny = z_sym.numel() // M, y_sym.numel() // M
+                for n in sorted(todo):
+                    ms = [m for m in range(M) if img[m] == n]
+                    measured[n].update((qs[m], size[m]) for m in ms)
+                    pick = _codec.budget_choice([qs[m] for m in ms], [size[m] for m in ms], budgets[n])
+                    if pick is None and rnd == 0:
+                        smallest = min(size[m] for m in ms)
+                        if strict:
+                            raise _codec.BudgetError(n, budgets[n], smallest)
+                        pick = qs[ms[0]]     # quality 0, the grid's first: the one stream that may exceed its budget
+                        del todo[n]
+                    if pick is not None:
+                        m = ms[[qs[k] for k in ms].index(pick)]
+                        chosen[n] = pick
+                        kept[n] = (z_sym[m * nz:(m + 1) * nz].clone(), kz[m], y_sym[m * ny:(m + 1) * ny].clone(), ky[m],
+                                   sigma[m:m + 1].clone(), mean[m:m + 1].clone(), size[m])
+                for n in list(todo):
+                    nxt = _codec.budget_next(measured[n], chosen[n])
+                    todo[n] = [] if nxt is None else _codec.budget_refine(chosen[n], nxt, candidates)
+                    if not todo[n]:
+                        del todo[n]     # chosen is S-1, or no float32 lies between it and the next one measured
+            self._use(chosen)
+            z_sym, y_sym = (torch.cat([k[i] for k in kept]) for i in (0, 2))
+            sigma, mean = (torch.cat([k[i] for k in kept]) for i in (4, 5))
+            kz, ky = ([k[i] for k in kept] for i in (1, 3))
+            sz = em.encode_symbols_seg(z_sym, kz, R)
+            sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), R, mean=mean)
+            streams = [self._pack_image(self._header(1, H, W, y, z, R, kz[n], ky[n], (h, w), n),
+                                        sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
+        finally:
+            self._end_call()
+        for n, s in enumerate(streams):
+            if len(s) != kept[n][6]:
+                raise RuntimeError(f"{who}: the stream of image {n} at quality {chosen[n]} holds {len(s)} bytes, "
+                                   f"{kept[n][6]} were measured")
+        return streams, chosen

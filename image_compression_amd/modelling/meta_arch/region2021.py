@@ -192,6 +192,10 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
             self._call_map(x.shape[0], *_codec.padded_size(*x.shape[2:]), "compress_each", each=True)
         return super().compress_each(x, steps_per_chunk)
 
+    def compress_each_to(self, x, budgets, steps_per_chunk=1024, candidates=8, rounds=2, strict=True):
+        raise ValueError("compress_each_to searches one quality per image: a byte budget for a quality map is not built; "
+                         "use GainedMeanScaleCompressor2018 for budgets")
+
     def _analyse(self, x, each=False):
         N, _, H, W = x.shape
         self._use_map(self._call_map(N, H, W, "compress_each" if each else "compress", each), x.device)

@@ -56,7 +56,8 @@ typedef struct ic_act {
 /* ---- library ---- */
 int ic_version(void);                 /* ABI version (monotonic; 3: ic_fact_net with IC_FACT_NET_MAXL layers; 4: ic_codec_*;
                                          additive to 4: ic_codec_*_seg, ic_pad_edge / ic_crop_clamp, and the mean-scale ops
-                                         ic_codec_symbolize_mean*, ic_center_round, ic_add_mean) */
+                                         ic_codec_symbolize_mean*, ic_center_round, ic_add_mean, and every later section
+                                         marked "additive to version 4") */
 int ic_device_sync_check(void* stream); /* hipStreamQuery-free no-op launch test */
 
 /* ---- Conv2d (k x k, stride, zero pad): y = conv(x, w) + b, act 0=none 1=relu
@@ -679,6 +680,28 @@ int ic_block_bits(const float* p, int N, int C, int Hm, int Wm, long long sn, lo
 int ic_block_sse(const float* a, const float* b, int N, int C, int H, int W, long long an, long long ac, long long ah,
                  long long aw, long long bn, long long bc, long long bh, long long bw, int shift, float* out,
                  void* stream);
+
+/* ---- coding to a byte budget (additive to version 4; GainedMeanScaleCompressor2018.compress_each_to).  The sizes
+ *      of candidate streams without their bytes, and the symbols of y for many (image, quality) candidates in one
+ *      launch.  IC_ERR_ARG before any launch for anything the text below excludes; no floating-point atomics. ---- */
+/* ic_codec_encode_seg without its output: lengths[segment * chunks per segment + chunk] = the byte count that call
+ * writes there for the same arguments, from the same per-step arithmetic (state update, ballot of the emitting
+ * lanes, popcount), with no store of a word or a state and so no workspace.  The same checks, the same LDS-or-pool
+ * rule per segment.  Neither allocates device memory nor waits for its stream. */
+int ic_codec_measure_seg(const int* sym, int nseg, long long seg_len, const unsigned char* rows, int C,
+                         const unsigned int* pool, size_t pool_words, int nrows, const int* seg_k,
+                         const long long* seg_off, int* seg_dev, int steps_per_chunk, unsigned int* lengths,
+                         void* stream);
+/* y: the latent of N images, dense (N, P, C) storage, channel fastest, read in place; candidate m of nseg
+ * (1 .. 65535) names its image img[m] in [0, N) (host array, checked, then copied to img_dev: nseg ints on the
+ * device), its gain row g[m] of g (nseg, C) and its mean mu[m] of mu (nseg, P, C):
+ *     sym[m][p][c] = the symbol of (y[img[m]][p][c] * g[m][c]) - mu[m][p][c]
+ * the product ic_channel_scale's one fp32 multiplication, the difference and the symbol those of
+ * ic_codec_symbolize_mean_seg: bit for bit these two calls on the gathered batch y[img].  kmax_dev / kmax_host as
+ * there: the maximum |symbol| of every candidate, one copy of the nseg maxima and one wait for the stream,
+ * IC_ERR_ARG (with kmax_host filled) when any exceeds IC_CODEC_KMAX. */
+int ic_gain_symbolize_seg(const float* y, long long N, long long P, int C, const float* g, const float* mu, int nseg,
+                          const int* img, int* img_dev, int* sym, int* kmax_dev, int* kmax_host, void* stream);
 
 #ifdef __cplusplus
 }
