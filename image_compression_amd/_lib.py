@@ -248,6 +248,14 @@ SIGNATURES = {
                                      c_void, c_int, c_void, c_void]),
     "ic_gain_symbolize_seg": (c_int, [c_void, c_ll, c_ll, c_int, c_void, c_void, c_int, P(c_int), c_void, c_void,
                                       c_void, P(c_int), c_void]),
+    # encode-time latent refinement: the Adam step with the Evaluate rule, the objective, keep-best (additive to
+    # ic_version 4)
+    "ic_refine_update": (c_int, [c_void, c_void, c_void, c_void, c_void, c_ll, c_ll, c_int, c_float, c_float, c_float,
+                                 c_void, c_void, c_void]),
+    "ic_refine_dist_grad": (c_int, [c_void, c_void, c_void, c_int, c_ll, c_void, c_void]),
+    "ic_refine_objective": (c_int, [c_void, c_void, c_void, c_int, c_ll, c_void, c_void]),
+    "ic_refine_keep": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_ll, c_int, c_void]),
+    "ic_refine_kmax": (c_int, [c_void, c_int, c_ll, c_void, c_void]),
 }
 
 _lib = None
@@ -273,6 +281,7 @@ gain_ops = _namespace("imgcomp_gain", "the gain units' gain vectors and channel 
 region_ops = _namespace("imgcomp_region", "scaling by a gain row per block and the block-weighted squared error")
 map_ops = _namespace("imgcomp_map", "the estimated bits and the squared error of every block")
 rate_ops = _namespace("imgcomp_rate", "the sizes and the symbols of candidate streams, for coding to a byte budget")
+refine_ops = _namespace("imgcomp_refine", "the bookkeeping of encode-time latent refinement")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

@@ -172,6 +172,31 @@ Sizes are not assumed monotone in the quality (the gain tables are learnt), so t
     an image whose choice is S-1 has no later round; nor has one for which no candidate of round 1 fits: that is a
         `BudgetError` (strict), or the image is coded at quality 0 and is the one stream that may exceed its budget.
 The result is optimal relative to the qualities measured, not to the interval.
+
+Encode-time latent refinement (`Compressor2018.compress_each_refined`): the rule
+---------------------------------------------------------------------------------
+The decoder's inputs stay fixed: the weights and the hyper-latent, and so (sigma, mu).  Only the integers of y change,
+so the streams are ordinary "ICRP" / "ICRQ" streams and `decompress_each` reads them as it reads any other.  For a
+call on N images, `_pad_each` and `_analyse(x, each=True)` give y, the symbols of z and kz (coded as `compress_each`
+codes them, never touched) and (sigma, mu) as the decoder will compute them.  The loop works in the coded domain,
+v0 = `_latent_gain(y)`; mu absent means that no subtraction and no addition is performed.
+    Evaluate(v):  s = symbol_of(v - mu) (one fp32 subtraction, the symbolizers' rule); y_hat = float(s) + mu (one fp32
+        addition); x_hat = `_reconstruct(_latent_ungain(y_hat))` on the padded batch; D_n = the sum of (x - x_hat)^2
+        over the padded image n; B_n = the sum over image n of the rate term clamp(-log2(p + 1e-10), 0, 50) of p, the
+        conditional likelihood of y_hat under (sigma, mu) (the kernel `conditional_likelihood` runs);
+        J_n = B_n + w_n D_n in fp64 with w_n = lambda_n / x.shape[1], image n's share of the training loss times its
+        pixel count; lambda_n is `distortion_loss_weight`, on the gained model `loss_weight(q_n)` of that image's
+        quality.
+    Gradient:  g = d(sum_n w_n D_n) / d y_hat + d(sum of the rate terms of p(v | sigma, mu)) / dv: the first term through
+        the clamp and g_s, passed straight through the rounding to v; the second the likelihood at the unrounded v.
+    Update:  Adam on v, moments m = u = 0 at the start, beta1 = 0.9, beta2 = 0.999, eps = 1e-8, the bias corrections
+        1 / (1 - beta^t) formed on the host in double and passed as fp32; every fp32 operation rounded once, in the
+        order csrc/refine.hip states.
+    Keep-best:  T + 1 evaluations, evaluation 0 the unrefined latent, whose symbols are bit for bit `compress_each`'s.
+        The symbols of evaluation t replace image n's kept symbols iff J_n(t) < best_n: strict, a NaN never wins, every
+        image decides alone.  After the last evaluation the kept symbols are coded: their per-image kmax first (the
+        same refusal above 2047 as `compress_each`), then `encode_symbols_seg` and `_pack_image`.
+So J_after <= J_before for every image, always, and steps = 0 gives `compress_each`'s bytes.
 """
 import math
 import struct

@@ -1948,6 +1948,169 @@ std::tuple<Tensor, std::vector<int64_t>> rate_gain_symbolize_seg_meta(const Tens
   return {symbols_out(mu), std::vector<int64_t>(img.size(), 0)};
 }
 
+// ---------------------------------------------------------------- encode-time latent refinement (imgcomp_refine)
+// The latent is (N, *, C) contiguous (channels-last storage); v, m and u are updated in place.  Nothing here copies to
+// the host or waits for the stream.  Inference only: no autograd node.
+void check_refine_latent(const Tensor& v, const std::optional<Tensor>& m, const std::optional<Tensor>& u,
+                         const std::optional<Tensor>& g, const std::optional<Tensor>& mu) {
+  TORCH_CHECK(v.dim() >= 2 && v.numel() > 0, "imgcomp_refine: v must be a non-empty (N, *, C) tensor, got ", v.sizes());
+  TORCH_CHECK(v.size(0) <= 65535 && v.size(-1) <= INT_MAX, "imgcomp_refine: v is too large: ", v.sizes());
+  const std::pair<const std::optional<Tensor>*, const char*> rest[] = {{&m, "m"}, {&u, "u"}, {&g, "g"}, {&mu, "mu"}};
+  for (const auto& [t, what] : rest)
+    if (t->has_value() && (*t)->defined())
+      TORCH_CHECK((*t)->sizes() == v.sizes(), "imgcomp_refine: ", what, " ", (*t)->sizes(), " must have v's shape ",
+                  v.sizes());
+  if (g.has_value() && g->defined())
+    TORCH_CHECK(m.has_value() && m->defined() && u.has_value() && u->defined(),
+                "imgcomp_refine: a step (g given) needs the moments m and u");
+}
+
+void check_refine_step(const std::optional<Tensor>& g, double lr, double c1, double c2) {
+  if (!g.has_value() || !g->defined()) return;
+  TORCH_CHECK_VALUE(std::isfinite(lr) && lr > 0.0, "imgcomp_refine: lr must be finite and positive, got ", lr);
+  TORCH_CHECK_VALUE(std::isfinite(c1) && c1 >= 1.0 && std::isfinite(c2) && c2 >= 1.0,
+                    "imgcomp_refine: the bias corrections 1 / (1 - beta^t) are finite and >= 1, got ", c1, " and ", c2);
+}
+
+std::tuple<Tensor, Tensor> refine_update(Tensor& v, const std::optional<Tensor>& m, const std::optional<Tensor>& u,
+                                         const std::optional<Tensor>& g, const std::optional<Tensor>& mu, double lr,
+                                         double c1, double c2) {
+  check_refine_latent(v, m, u, g, mu);
+  check_refine_step(g, lr, c1, c2);
+  check_operand(v, "v");
+  TORCH_CHECK(v.is_contiguous(), "imgcomp_refine: v must be contiguous");
+  const std::pair<const std::optional<Tensor>*, const char*> rest[] = {{&m, "m"}, {&u, "u"}, {&g, "g"}, {&mu, "mu"}};
+  for (const auto& [t, what] : rest)
+    if (t->has_value() && (*t)->defined()) {
+      check_operand(**t, what);
+      TORCH_CHECK((*t)->is_contiguous() && (*t)->device() == v.device(), "imgcomp_refine: ", what,
+                  " must be contiguous and on v's device");
+    }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(v.device());
+  Tensor sym = symbols_out(v);
+  Tensor y_hat = at::empty(v.sizes(), v.options());
+  const int64_t N = v.size(0), C = v.size(-1);
+  check_rc(ic_refine_update(v.data_ptr<float>(), opt_ptr(m), opt_ptr(u), opt_ptr(g), opt_ptr(mu), N, v.numel() / N / C,
+                            (int)C, (float)lr, (float)c1, (float)c2, sym.data_ptr<int>(), y_hat.data_ptr<float>(),
+                            stream_of(v)),
+           "refine_update");
+  return {sym, y_hat};
+}
+
+void check_refine_images(const Tensor& x, const Tensor& x_hat, const Tensor& w) {
+  TORCH_CHECK(x.dim() >= 2 && x.numel() > 0 && x.size(0) <= 65535, "imgcomp_refine: x must be a non-empty (N, *) batch of "
+              "at most 65535 images, got ", x.sizes());
+  TORCH_CHECK(x_hat.sizes() == x.sizes(), "imgcomp_refine: x_hat ", x_hat.sizes(), " must have x's shape ", x.sizes());
+  TORCH_CHECK(w.dim() == 1 && w.size(0) == x.size(0) && w.scalar_type() == at::kDouble,
+              "imgcomp_refine: w must hold one float64 weight per image");
+}
+
+Tensor refine_dist_grad(const Tensor& x, const Tensor& x_hat, const Tensor& w) {
+  check_refine_images(x, x_hat, w);
+  check_operand(x, "x");
+  check_operand(x_hat, "x_hat");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && x.is_contiguous() && x_hat.is_contiguous() &&
+                  x.device() == x_hat.device() && x.device() == w.device(),
+              "imgcomp_refine: x, x_hat and w must be contiguous on one ROCm device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor gx = at::empty(x.sizes(), x.options());
+  check_rc(ic_refine_dist_grad(x.data_ptr<float>(), x_hat.data_ptr<float>(), w.data_ptr<double>(), (int)x.size(0),
+                               x.numel() / x.size(0), gx.data_ptr<float>(), stream_of(x)),
+           "refine_dist_grad");
+  return gx;
+}
+
+void check_refine_maps(const Tensor& bits, const Tensor& sse, const Tensor& w) {
+  TORCH_CHECK(bits.dim() >= 2 && bits.numel() > 0 && bits.size(0) <= 65535,
+              "imgcomp_refine: bits must be a non-empty (N, *) map of at most 65535 images, got ", bits.sizes());
+  TORCH_CHECK(sse.sizes() == bits.sizes(), "imgcomp_refine: the maps must share a shape, got ", bits.sizes(), " and ",
+              sse.sizes());
+  TORCH_CHECK(w.dim() == 1 && w.size(0) == bits.size(0) && w.scalar_type() == at::kDouble,
+              "imgcomp_refine: w must hold one float64 weight per image");
+}
+
+Tensor refine_objective(const Tensor& bits, const Tensor& sse, const Tensor& w) {
+  check_refine_maps(bits, sse, w);
+  check_operand(bits, "bits");
+  check_operand(sse, "sse");
+  TORCH_CHECK(w.is_cuda() && w.is_contiguous() && bits.is_contiguous() && sse.is_contiguous() &&
+                  bits.device() == sse.device() && bits.device() == w.device(),
+              "imgcomp_refine: bits, sse and w must be contiguous on one ROCm device");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(bits.device());
+  const int64_t N = bits.size(0);
+  Tensor out = at::empty({3, N}, w.options());
+  check_rc(ic_refine_objective(bits.data_ptr<float>(), sse.data_ptr<float>(), w.data_ptr<double>(), (int)N,
+                               bits.numel() / N, out.data_ptr<double>(), stream_of(bits)),
+           "refine_objective");
+  return out;
+}
+
+void check_refine_keep(const Tensor& sym, const Tensor& best_sym, const Tensor& obj, const Tensor& best,
+                       const Tensor& best_step, int64_t step) {
+  TORCH_CHECK(obj.dim() == 2 && obj.size(0) == 3 && obj.size(1) >= 1 && obj.size(1) <= 65535 &&
+                  obj.scalar_type() == at::kDouble,
+              "imgcomp_refine: obj must be float64 (3, N), got ", obj.sizes());
+  const int64_t N = obj.size(1);
+  TORCH_CHECK(best.sizes() == obj.sizes() && best.scalar_type() == at::kDouble,
+              "imgcomp_refine: best must be float64 (3, N) like obj, got ", best.sizes());
+  TORCH_CHECK(best_step.dim() == 1 && best_step.size(0) == N && best_step.scalar_type() == at::kInt,
+              "imgcomp_refine: best_step must be int32 (N)");
+  TORCH_CHECK(sym.scalar_type() == at::kInt && best_sym.scalar_type() == at::kInt && sym.numel() > 0 &&
+                  sym.numel() == best_sym.numel() && sym.numel() % N == 0,
+              "imgcomp_refine: sym and best_sym must be int32 and hold the ", N, " images' symbols back to back");
+  TORCH_CHECK_VALUE(step >= 0 && step <= INT_MAX, "imgcomp_refine: step must be >= 0, got ", step);
+}
+
+void refine_keep(const Tensor& sym, Tensor& best_sym, const Tensor& obj, Tensor& best, Tensor& best_step, int64_t step) {
+  check_refine_keep(sym, best_sym, obj, best, best_step, step);
+  for (const Tensor* t : std::initializer_list<const Tensor*>{&sym, &best_sym, &obj, &best, &best_step})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() && t->device() == sym.device(),
+                "imgcomp_refine: every operand of keep must be contiguous on one ROCm device");
+  TORCH_CHECK(sym.data_ptr() != best_sym.data_ptr(), "imgcomp_refine: sym and best_sym must be two buffers");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  const int64_t N = obj.size(1);
+  for (int mode = 0; mode < 2; ++mode)   // the symbols first, then the scalars the comparison reads
+    check_rc(ic_refine_keep(sym.data_ptr<int>(), best_sym.data_ptr<int>(), obj.data_ptr<double>(), best.data_ptr<double>(),
+                            best_step.data_ptr<int>(), (int)step, (int)N, sym.numel() / N, mode, stream_of(sym)),
+             "refine_keep");
+}
+
+Tensor refine_kmax(const Tensor& sym, int64_t nseg) {
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && sym.scalar_type() == at::kInt && sym.numel() > 0 && sym.numel() % nseg == 0,
+              "imgcomp_refine: sym must be int32 and make ", nseg, " equal segments");
+  check_codec(sym, at::kInt, "sym");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  Tensor kmax = at::empty({nseg}, sym.options());
+  check_rc(ic_refine_kmax(sym.data_ptr<int>(), (int)nseg, sym.numel() / nseg, kmax.data_ptr<int>(), stream_of(sym)),
+           "refine_kmax");
+  return kmax;
+}
+
+std::tuple<Tensor, Tensor> refine_update_meta(Tensor& v, const std::optional<Tensor>& m, const std::optional<Tensor>& u,
+                                              const std::optional<Tensor>& g, const std::optional<Tensor>& mu, double lr,
+                                              double c1, double c2) {
+  check_refine_latent(v, m, u, g, mu);
+  check_refine_step(g, lr, c1, c2);
+  return {symbols_out(v), at::empty(v.sizes(), v.options())};
+}
+Tensor refine_dist_grad_meta(const Tensor& x, const Tensor& x_hat, const Tensor& w) {
+  check_refine_images(x, x_hat, w);
+  return at::empty(x.sizes(), x.options());
+}
+Tensor refine_objective_meta(const Tensor& bits, const Tensor& sse, const Tensor& w) {
+  check_refine_maps(bits, sse, w);
+  return at::empty({3, bits.size(0)}, w.options());
+}
+void refine_keep_meta(const Tensor& sym, Tensor& best_sym, const Tensor& obj, Tensor& best, Tensor& best_step,
+                      int64_t step) {
+  check_refine_keep(sym, best_sym, obj, best, best_step, step);
+}
+Tensor refine_kmax_meta(const Tensor& sym, int64_t nseg) {
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && sym.scalar_type() == at::kInt && sym.numel() > 0 && sym.numel() % nseg == 0,
+              "imgcomp_refine: sym must be int32 and make ", nseg, " equal segments");
+  return at::empty({nseg}, sym.options());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -2333,4 +2496,31 @@ TORCH_LIBRARY_IMPL(imgcomp_rate, CUDA, m) {
 TORCH_LIBRARY_IMPL(imgcomp_rate, Meta, m) {
   m.impl("measure_seg", rate_measure_seg_meta);
   m.impl("gain_symbolize_seg", rate_gain_symbolize_seg_meta);
+}
+
+// Encode-time latent refinement (Compressor2018.compress_each_refined): additive, in a namespace of its own.
+// Inference only: no autograd node.  `update` steps v, m and u in place; `keep` writes best_sym, best and best_step.
+TORCH_LIBRARY(imgcomp_refine, m) {
+  m.def("update(Tensor(a!) v, Tensor(b!)? m, Tensor(c!)? u, Tensor? g, Tensor? mu, float lr, float c1, float c2) -> "
+        "(Tensor, Tensor)");
+  m.def("dist_grad(Tensor x, Tensor x_hat, Tensor w) -> Tensor");
+  m.def("objective(Tensor bits, Tensor sse, Tensor w) -> Tensor");
+  m.def("keep(Tensor sym, Tensor(a!) best_sym, Tensor obj, Tensor(b!) best, Tensor(c!) best_step, int step) -> ()");
+  m.def("kmax(Tensor sym, int nseg) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_refine, CUDA, m) {
+  m.impl("update", refine_update);
+  m.impl("dist_grad", refine_dist_grad);
+  m.impl("objective", refine_objective);
+  m.impl("keep", refine_keep);
+  m.impl("kmax", refine_kmax);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_refine, Meta, m) {
+  m.impl("update", refine_update_meta);
+  m.impl("dist_grad", refine_dist_grad_meta);
+  m.impl("objective", refine_objective_meta);
+  m.impl("keep", refine_keep_meta);
+  m.impl("kmax", refine_kmax_meta);
 }

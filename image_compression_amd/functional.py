@@ -1153,6 +1153,60 @@ def block_sse(a, b, shift=6):
     return _lib.map_ops().block_sse(a, b, _map_shift(shift))
 
 
+# ============================================================== encode-time latent refinement
+# Thin wrappers of torch.ops.imgcomp_refine (csrc/refine.hip): the bookkeeping of Compressor2018.compress_each_refined.
+# Inference only, on the current stream; none of them copies to the host or waits for the stream.
+class RoundThroughFn(Function):
+    """y_hat, the value of `refine_update`'s Evaluate rule at v, as a function of v whose gradient passes straight
+    through the rounding to v."""
+
+    @staticmethod
+    def forward(ctx, v, y_hat):
+        return y_hat.view_as(y_hat)
+
+    @staticmethod
+    def backward(ctx, g):
+        return g, None
+
+
+def refine_update(v, m, u, g, mu, lr=0.0, c1=1.0, c2=1.0):
+    """One pass over the latent v (N, *, C), contiguous channels-last storage.  With a gradient g: the Adam step on v and
+    its moments m, u, all three in place, at the learning rate lr with the bias corrections c1 = 1 / (1 - 0.9^t) and
+    c2 = 1 / (1 - 0.999^t) (the fp32 operation order: csrc/refine.hip).  Then, with or without a step, the Evaluate
+    rule on v -> (int32 symbols rint(v - mu) flattened, y_hat = symbols + mu shaped like v); mu None: about 0."""
+    _on_device("refine_update", v=v, m=m, u=u, g=g, mu=mu)
+    _inference_only("refine_update", v=v, m=m, u=u, g=g, mu=mu)
+    return _lib.refine_ops().update(v, m, u, g, mu, float(lr), float(c1), float(c2))
+
+
+def refine_dist_grad(x, x_hat, w):
+    """(float32)(2 w[n]) * (x_hat - x): the gradient at x_hat of sum_n w[n] D_n, D_n the squared error of image n;
+    x, x_hat contiguous (N, *), w float64 (N) on the device."""
+    _on_device("refine_dist_grad", x=x, x_hat=x_hat, w=w)
+    return _lib.refine_ops().dist_grad(x.detach(), x_hat.detach(), w)
+
+
+def refine_objective(bits, sse, w):
+    """float64 (3, N): B_n and D_n, the sums of image n's values of the maps `block_bits` / `block_sse` made (both
+    (N, Hb, Wb)) in ascending block order in fp64, and J_n = B_n + w[n] D_n; w float64 (N) on the device."""
+    _on_device("refine_objective", bits=bits, sse=sse, w=w)
+    return _lib.refine_ops().objective(bits, sse, w)
+
+
+def refine_keep(sym, best_sym, obj, best, best_step, step):
+    """Keep-best, image by image: where obj[2, n] < best[2, n] (strict; a NaN never wins) image n's segment of `sym`
+    replaces that of `best_sym`, best[:, n] = obj[:, n] and best_step[n] = step; everything else is left alone.  Two
+    launches: the symbols, then the scalars the comparison reads."""
+    _on_device("refine_keep", sym=sym, best_sym=best_sym, obj=obj, best=best, best_step=best_step)
+    _lib.refine_ops().keep(sym, best_sym, obj, best, best_step, int(step))
+
+
+def refine_kmax(sym, nseg):
+    """int32 (nseg) on the device: max |symbol| of each of the nseg equal segments of `sym`."""
+    _on_device("refine_kmax", sym=sym)
+    return _lib.refine_ops().kmax(sym, int(nseg))
+
+
 class SqDiffFn(Function):
     """(a - b)^2 elementwise: nn.MSELoss(reduction='none')."""
 

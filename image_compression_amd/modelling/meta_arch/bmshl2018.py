@@ -4,7 +4,9 @@ modelling/meta_arch/bmshl2018.py:49-110), every tensor op on HIP kernels.
 forward(x) -> (x_tilde.detach(), losses) with losses =
 {z_entropy, y_entropy, bpp, total_loss, <distortion names>}; only
 total_loss carries grad."""
+import math
 import os
+from numbers import Real
 from typing import NamedTuple, Optional
 
 import numpy as np
@@ -14,7 +16,9 @@ import torch.nn as nn
 from ... import _lib
 from ... import codec as _codec
 from ... import noise as _noise
-from ...functional import AbsFn, NonNegMultiFn, block_bits, block_sse, factorized, route_weight_gradients
+from ...functional import (AbsFn, CELossFn, NonNegFn, NonNegMultiFn, RoundThroughFn, _match, _to_last, block_bits,
+                           block_sse, conditional_likelihood, factorized, refine_dist_grad, refine_keep, refine_kmax,
+                           refine_objective, refine_update, route_weight_gradients)
 from ..blocks.entropy_model import symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
@@ -34,6 +38,18 @@ class RDMap(NamedTuple):
     x_hat: torch.Tensor     # (N, 3, h, w), the eval forward's reconstruction (cropped when the image was padded)
     p_y: Optional[torch.Tensor] = None   # with likelihoods=True: (N, M, H / 16, W / 16), what bits_y sums
     p_z: Optional[torch.Tensor] = None   # (N, C_z, H / 64, W / 64), what bits_z sums
+
+
+class RefineReport(NamedTuple):
+    """What `Compressor2018.compress_each_refined` returns beside the streams: per-image lists.  J = B + w D in bits
+    (codec.py: the refinement rule), B the estimated bits of y and D the squared error over the padded image."""
+    before: list        # J of the unrefined latent (evaluation 0)
+    after: list         # J of the symbols that were coded
+    bits_before: list
+    bits_after: list
+    sse_before: list
+    sse_after: list
+    step: list          # the evaluation that won; 0: the unrefined latent
 
 
 def block_pixels(h, w):
@@ -447,6 +463,131 @@ class Compressor2018(nn.Module):
             for m, img in zip(idx, self._reconstruct_each(y_hat, hs)):
                 out[m] = img
         return out
+
+    # ---- encode-time latent refinement: lower R + lambda D for this image, same decoder (codec.py states the rule)
+    refine_refusal = None    # a model whose streams the rule does not cover says why here
+
+    def _refine_weights(self, N):
+        """[lambda_n]: the distortion weight of every image of a `compress_each_refined` call (after `_analyse`)."""
+        return [float(self.distortion_loss_weight)] * N
+
+    def _check_refine(self, steps, lr):
+        """The refusals of `compress_each_refined`, in front of any launch."""
+        who = "compress_each_refined"
+        if self.refine_refusal:
+            raise ValueError(f"{who}: {self.refine_refusal}")
+        if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)) or steps < 0:
+            raise ValueError(f"{who}: steps is an integer >= 0, got {steps!r}")
+        if isinstance(lr, bool) or not isinstance(lr, Real) or not math.isfinite(lr) or not lr > 0:
+            raise ValueError(f"{who}: lr is a finite positive number, got {lr!r}")
+        if list(self.distortion_loss_fns) != ["MSE"]:
+            raise ValueError(f"{who}: the objective is R + lambda MSE; this model's distortion is "
+                             f"{list(self.distortion_loss_fns)}")
+
+    def compress_each_refined(self, x, steps=8, lr=0.1, steps_per_chunk=1024):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> (a list of N streams as `compress_each` writes them, a
+        RefineReport): every image coded with the integers of y that gave it the lowest J = R + lambda D among the
+        unrefined latent and `steps` Adam steps (learning rate `lr`) on the image's own objective.  The decoder's
+        inputs (the weights, the hyper-latent and so sigma and mu) are untouched: `decompress_each` reads the streams
+        as any other, and steps = 0 gives `compress_each`'s bytes.  J_after <= J_before for every image.  The defaults
+        come from an experiment on untrained weights; they are not validated on trained ones.
+
+        The rule (codec.py has the whole of it).  In the coded domain v0 = `_latent_gain(y)`:
+          Evaluate(v): s = symbol_of(v - mu), y_hat = float(s) + mu, x_hat = `_reconstruct(_latent_ungain(y_hat))`,
+            D_n the squared error over the padded image, B_n the rate terms of the conditional likelihood of y_hat
+            under (sigma, mu), J_n = B_n + w_n D_n with w_n = lambda_n / x.shape[1];
+          Gradient: d(sum w_n D_n) / d y_hat, straight through the rounding, plus d(rate at the unrounded v) / dv;
+          Update: Adam on v (beta 0.9 / 0.999, eps 1e-8, bias corrections from the host; csrc/refine.hip);
+          Keep-best: evaluation t replaces image n's kept symbols iff J_n(t) < best_n (strict, a NaN never wins).
+
+        The loop runs g_s forward and its input-gradient backward and no weight-gradient kernel: every parameter has
+        requires_grad off for the duration, and it and every .grad are afterwards what they were.  The whole loop is
+        enqueued without a copy to the host or a wait; the one copy, after the last evaluation, brings the N maxima
+        of the kept symbols and the report."""
+        from ..layers.gdn import NonNegativeParam
+        who = "compress_each_refined"
+        self._check_refine(steps, lr)
+        self._codable_each()
+        em, cm, T, R = self.entropy_model, self.conditional_model, int(steps), steps_per_chunk
+        params = list(self.parameters())
+        flags = [p.requires_grad for p in params]
+        try:
+            for p in params:
+                p.requires_grad_(False)
+            with torch.no_grad():
+                x, (N, h, w, H, W) = self._pad_each(x)
+                x = x.contiguous()
+                y, z, z_sym, kz, (sigma, mean) = self._analyse(x, each=True)
+                v0 = self._latent_gain(y)
+                shape = tuple(v0.shape)
+                v = _to_last(v0)
+                if v.data_ptr() == v0.data_ptr():
+                    v = v.clone()                    # stepped in place: never the model's own tensor
+                logical = symbols_as_tensor(v, shape)
+                sigma = _match(sigma.expand_as(logical), logical)
+                mean = None if mean is None else _match(mean.expand_as(logical), logical)
+                mu = None if mean is None else _to_last(mean)
+                m, u = torch.zeros_like(v), torch.zeros_like(v)
+                wts = torch.tensor([lam / x.shape[1] for lam in self._refine_weights(N)], dtype=torch.float64).to(x.device)
+                best = torch.full((3, N), float("inf"), dtype=torch.float64, device=x.device)
+                best_step = torch.zeros(N, dtype=torch.int32, device=x.device)
+                one = torch.ones((), device=x.device)
+                gdns = [mod for mod in self.synthesis_transform.modules() if isinstance(mod, NonNegativeParam)]
+                pre = [NonNegFn.apply(mod.param, float(mod.bound), float(mod.pedestal)) for mod in gdns]
+            y_shift = (_codec.MAP_BLOCK // _codec.Y_DOWN).bit_length() - 1
+            first = best_sym = g = None
+            for t in range(T + 1):
+                with torch.no_grad():
+                    if t == 0:
+                        sym, y_hat = refine_update(v, None, None, None, mu)
+                    else:
+                        sym, y_hat = refine_update(v, m, u, _to_last(g), mu, lr, 1.0 / (1.0 - 0.9 ** t),
+                                                   1.0 / (1.0 - 0.999 ** t))
+                    y_hat = symbols_as_tensor(y_hat, shape)
+                for mod, val in zip(gdns, pre):       # g_s's GDN parameters, re-parameterised once for the call
+                    mod.__dict__["_pre"] = val
+                with torch.set_grad_enabled(t < T):
+                    if t < T:
+                        leaf = symbols_as_tensor(v, shape).detach().requires_grad_(True)
+                        y_hat = RoundThroughFn.apply(leaf, y_hat)
+                    x_hat = self._reconstruct(self._latent_ungain(y_hat))
+                    if t < T:
+                        rate = CELossFn.apply(conditional_likelihood(leaf, sigma, mean, cm.KIND, cm.bin))
+                with torch.no_grad():
+                    p = conditional_likelihood(y_hat.detach(), sigma, mean, cm.KIND, cm.bin)
+                    xd = x_hat.detach().contiguous()
+                    obj = refine_objective(block_bits(p, y_shift), block_sse(x, xd, _codec.MAP_BLOCK.bit_length() - 1), wts)
+                    if t == 0:
+                        # the unrefined latent, `compress_each`'s symbols: kept even where its J is a NaN
+                        first, best_sym = obj, sym.clone()
+                    refine_keep(sym, best_sym, obj, best, best_step, t)
+                    if t < T:
+                        gx = refine_dist_grad(x, xd, wts)
+                if t < T:
+                    g, = torch.autograd.grad([x_hat, rate], [leaf], [gx, one])
+                    del leaf, rate
+                del x_hat
+            with torch.no_grad():
+                kd = refine_kmax(best_sym, N)
+                # the one copy to the host: the report and the N maxima
+                out = torch.cat([first.reshape(-1), best.reshape(-1), best_step.double(), kd.double()]).cpu().numpy()
+                ky = [int(k) for k in out[7 * N:]]
+                for n, k in enumerate(ky):
+                    if k > _codec.KMAX_LIMIT:
+                        raise ValueError(f"{who}: image {n} has a symbol of magnitude {k}, which exceeds the coder's "
+                                         f"limit of {_codec.KMAX_LIMIT}")
+                sz = em.encode_symbols_seg(z_sym, kz, R)
+                sy = cm.encode_symbols_seg(best_sym, ky, sigma, R, mean=mean)
+                streams = [self._pack_image(self._header(1, H, W, y, z, R, kz[n], ky[n], (h, w), n),
+                                            sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
+        finally:
+            for p, f in zip(params, flags):
+                p.requires_grad_(f)
+            self._clear_reparameterised()
+            self._end_call()
+        rows = [[float(a) for a in out[k * N:(k + 1) * N]] for k in range(6)]
+        return streams, RefineReport(before=rows[2], after=rows[5], bits_before=rows[0], bits_after=rows[3],
+                                     sse_before=rows[1], sse_after=rows[4], step=[int(a) for a in out[6 * N:7 * N]])
 
     # ---- rate and distortion maps: where the bits go and where the error is, block by block, from one eval pass
     def _check_call(self, N, H, W, who):

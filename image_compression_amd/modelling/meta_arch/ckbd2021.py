@@ -55,6 +55,9 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
     used and receive a gradient of exactly 0.  State dict: MeanScaleCompressor2018's plus
     context_mean.{weight,bias} and context_scale.{weight,bias}, all zero in a fresh model."""
 
+    refine_refusal = ("CheckerboardCompressor2018 is not covered: the non-anchors' (sigma, mu) depend on y, so moving y "
+                      "moves the decoder's inputs")
+
     def __init__(self, cfg):
         super().__init__(cfg)
         # after every inherited module: their initial values are MeanScaleCompressor2018's from the same seed

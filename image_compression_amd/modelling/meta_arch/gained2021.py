@@ -197,6 +197,11 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
     def _begin_decode(self, headers):
         self._use([h.quality for h in headers])
 
+    def _refine_weights(self, N):
+        """`loss_weight` of every image's quality: the call's qualities give both the gains and lambda_n."""
+        qs = self._qualities if len(self._qualities) == N else self._qualities * N
+        return [float(self.loss_weight(q)) for q in qs]
+
     # ---- coding to a byte budget: the search rule of codec.py on sizes the coder itself reports
     def _check_budget_call(self, x, budgets, steps_per_chunk, candidates, rounds):
         """The budgets of a `compress_each_to` call, one int per image; every check in front of any launch."""

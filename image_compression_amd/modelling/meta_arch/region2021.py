@@ -49,6 +49,8 @@ def _as_codes(codes):
 class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
     graph_refusal = ("RegionGainedMeanScaleCompressor2018 draws its quality map and its block weights on the host every "
                      "step: a captured graph would replay one map for ever; use TrainStep(graph=False)")
+    refine_refusal = ("RegionGainedMeanScaleCompressor2018 is not covered: its distortion is weighed by a quality map, "
+                      "which the objective R + lambda MSE does not know; use GainedMeanScaleCompressor2018")
 
     def __init__(self, cfg):
         names, reduction = list(cfg.MODEL.LOSS.DISTORTION_LOSS_NAMES), cfg.MODEL.LOSS.REDUCTION

@@ -703,6 +703,38 @@ int ic_codec_measure_seg(const int* sym, int nseg, long long seg_len, const unsi
 int ic_gain_symbolize_seg(const float* y, long long N, long long P, int C, const float* g, const float* mu, int nseg,
                           const int* img, int* img_dev, int* sym, int* kmax_dev, int* kmax_host, void* stream);
 
+/* ---- encode-time latent refinement (additive to version 4; Compressor2018.compress_each_refined).  The bookkeeping
+ *      of the loop that moves the coded latent v by Adam steps on every image's own R + lambda D and keeps the best
+ *      integers it saw.  IC_ERR_ARG before any launch for a null pointer, N outside 1 .. 65535, an extent below 1 or
+ *      anything the text below excludes.  None of them allocates, copies to the host or waits for its stream; no
+ *      floating-point atomics, every sum in one fixed order. ---- */
+/* v, m, u, g, mu, sym, y_hat: dense (N, P, C) storage, channel fastest.  With g: the Adam step on v in place (moments
+ * m, u in place; lr finite and positive, c1 = 1 / (1 - 0.9^t) and c2 = 1 / (1 - 0.999^t) as fp32, both >= 1), every
+ * fp32 operation rounded once and none contracted (the order: csrc/refine.hip):
+ *     m = 0.9f m + 0.1f g;  u = 0.999f u + 0.001f (g g);  v = v - (lr (m c1)) / (sqrtf(u c2) + 1e-8f)
+ * g NULL: no step, v, m and u are not written (m and u may be NULL).  Then the Evaluate rule on v:
+ *     sym = the symbol of v - mu (ic_codec_symbolize_mean_seg's);  y_hat = (float)sym + mu (ic_add_mean's)
+ * mu NULL: neither the subtraction nor the addition is performed. */
+int ic_refine_update(float* v, float* m, float* u, const float* g, const float* mu, long long N, long long P, int C,
+                     float lr, float c1, float c2, int* sym, float* y_hat, void* stream);
+/* gx = (float)(2 w[n]) * (x_hat - x) over the `len` elements of image n: the gradient of sum_n w[n] D_n at x_hat */
+int ic_refine_dist_grad(const float* x, const float* x_hat, const double* w, int N, long long len, float* gx,
+                        void* stream);
+/* bits, sse: the maps of ic_block_bits / ic_block_sse, (N, nb) dense.  out (3, N) fp64: out[0][n] = B_n and
+ * out[1][n] = D_n, each the sum of image n's nb values in ascending order in fp64, out[2][n] = J_n = B_n + w[n] D_n
+ * (one fp64 product, one fp64 sum) */
+int ic_refine_objective(const float* bits, const float* sse, const double* w, int N, long long nb, double* out,
+                        void* stream);
+/* obj, best: (3, N) fp64 as ic_refine_objective writes them.  mode 0: image n's `len` symbols of sym are copied to
+ * best_sym where obj[2][n] < best[2][n] (strict; false for a NaN on either side); obj and best are only read.
+ * mode 1 (a second launch, after mode 0): where the same comparison holds, best[.][n] = obj[.][n] and
+ * best_step[n] = step (>= 0); sym and best_sym are not looked at. */
+int ic_refine_keep(const int* sym, int* best_sym, const double* obj, double* best, int* best_step, int step, int N,
+                   long long len, int mode, void* stream);
+/* kmax[n] = the maximum |symbol| of image n's `len` symbols (INT_MAX for INT_MIN), on the device: one integer
+ * atomicMax per block after a memset on the stream */
+int ic_refine_kmax(const int* sym, int N, long long len, int* kmax, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -41,6 +41,10 @@ images of a call each at their own candidate) and (b) by compress_each_to, alter
 measure_seg beside encode_seg + compact_seg and the fused symbolizer beside gather + channel_scale +
 symbolize_mean_seg on one round's candidates, by device events.  --out profiles/codec_budget_bench.json.
 
+--refine T [--arch NAME] [--scale 32] times compress_each and compress_each_refined with T steps on 8 x 3 x 512 x 768
+images (ms per image, best of --reps wall times), the cost of one refinement step by device events ((T steps - 0
+steps) / T) and, beside it, one g_s forward with its input-gradient backward.  --out profiles/codec_refine_bench.json.
+
 --context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
 --each works on it too (its loop arm is then the fused model's own compress / decompress).
 
@@ -222,11 +226,18 @@ def main():
     ap.add_argument("--budget", type=int, default=0, metavar="BYTES",
                     help="8 x 3 x 512 x 768 images coded to BYTES each: the naive search from compress_each against "
                          "compress_each_to (--candidates, --rounds)")
+    ap.add_argument("--refine", type=int, default=None, metavar="T",
+                    help="compress_each beside compress_each_refined with T steps at 8 x 3 x 512 x 768; ms per step")
     ap.add_argument("--candidates", type=int, default=8, help="candidate qualities per round of --budget")
     ap.add_argument("--rounds", type=int, default=2, help="rounds of --budget")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.refine is not None:
+        if args.refine < 0:
+            ap.error("--refine: a number of steps >= 0")
+        _emit(refine_bench(args), args.out)
+        return
     if args.budget:
         _emit(budget_bench(args), args.out)
         return
@@ -919,6 +930,71 @@ def budget_bench(args):
         out["kernels_kmax_y"] = [min(ky), max(ky)]
         out["kernels_note"] = ("device events around one call; the two symbolizers include their copy of the maxima and "
                                "their stream wait, encode_seg_and_compact_seg allocates its worst-case buffers")
+    return out
+
+
+def refine_bench(args):
+    """--refine T: compress_each beside compress_each_refined with T steps on 8 x 3 x 512 x 768 images, alternately in
+    one process (wall time, device synchronised inside the timed region); the cost of one refinement step by device
+    events, as (the call with T steps - the call with 0 steps) / T; and beside it one g_s forward with its
+    input-gradient backward on the same latent, also by device events: the structure says a step costs about that."""
+    from image_compression_amd import functional as F
+    N, H, W, reps, T = 8, 512, 768, args.reps, args.refine
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(N, 3, H, W, device="cuda", generator=g)
+    model, cfg = _build(args.arch, args.scale)
+    out = {"metric": f"compress_each and compress_each_refined({T} steps, lr 0.1) at {N} x 3 x {H} x {W}, "
+                     f"{cfg.MODEL.COMPUTE_DTYPE}, best of {reps} alternating reps", "unit": "ms", "reps": reps, "steps": T,
+           "arch": args.arch, "weight_scale": args.scale,
+           "data": "synthetic uniform [0,1) images resident in HBM; random-init weights (reference init, seed 0)"}
+    calls = {"compress_each": lambda: model.compress_each(x),
+             "compress_each_refined_0": lambda: model.compress_each_refined(x, steps=0),
+             "compress_each_refined": lambda: model.compress_each_refined(x, steps=T)}
+    for fn in calls.values():
+        for _ in range(2):
+            fn()
+    wall, dev = {k: [] for k in calls}, {k: [] for k in calls}
+    for _ in range(reps):
+        for k, fn in calls.items():
+            wall[k].append(_wall(fn, 1))
+        for k, fn in calls.items():
+            dev[k].append(_events(fn, 1))
+    for k in calls:
+        out[f"{k}_ms_per_image"] = round(min(wall[k]) / N, 4)
+        out[f"{k}_all_ms"] = [round(u, 3) for u in wall[k]]
+        out[f"{k}_events_ms"] = round(min(dev[k]), 3)
+    out["refined_over_plain"] = round(min(wall["compress_each_refined"]) / min(wall["compress_each"]), 3)
+    if T:
+        out["step_ms_by_events"] = round((min(dev["compress_each_refined"]) - min(dev["compress_each_refined_0"])) / T, 4)
+    # one g_s forward and its input-gradient backward on the call's own latent shape, no weight gradient
+    streams, report = model.compress_each_refined(x, steps=T)
+    out["stream_bytes"] = [len(s) for s in streams]
+    out["plain_stream_bytes"] = [len(s) for s in model.compress_each(x)]
+    out["j_before"], out["j_after"], out["winning_evaluation"] = report.before, report.after, report.step
+    params = list(model.parameters())
+    flags = [p.requires_grad for p in params]
+    try:
+        for p in params:
+            p.requires_grad_(False)
+        with torch.no_grad():
+            y = model.analysis_transform(x)
+            gx = torch.ones(N, 3, H, W, device="cuda")
+
+        def gs_pair():
+            leaf = y.detach().requires_grad_(True)
+            torch.autograd.grad([model._reconstruct(leaf)], [leaf], [gx])
+
+        with F.record_plans() as log:
+            gs_pair()
+        out["g_s_pair_ops"] = sorted({p["op"] for p in log})
+        gs_pair()
+        out["g_s_forward_and_dgrad_ms_by_events"] = round(min(_events(gs_pair, 1) for _ in range(reps)), 4)
+    finally:
+        for p, f in zip(params, flags):
+            p.requires_grad_(f)
+        model._clear_reparameterised()
+    if T:
+        out["step_over_g_s_pair"] = round(out["step_ms_by_events"] / out["g_s_forward_and_dgrad_ms_by_events"], 3)
     return out
 
 
