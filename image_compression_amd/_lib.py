@@ -62,6 +62,11 @@ class ICPlan(ctypes.Structure):
                 ("im2col", c_int), ("variant", c_int), ("blocks", c_ll)]
 
 
+class ICWindow(ctypes.Structure):
+    _fields_ = [("base", c_ll), ("table", c_ll), ("hy", c_int), ("wy", c_int), ("K", c_int), ("r0", c_int),
+                ("c0", c_int), ("k0", c_int), ("k1", c_int)]
+
+
 P = ctypes.POINTER
 _ACT = P(ICAct)
 
@@ -256,6 +261,11 @@ SIGNATURES = {
     "ic_refine_objective": (c_int, [c_void, c_void, c_void, c_int, c_ll, c_void, c_void]),
     "ic_refine_keep": (c_int, [c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_ll, c_int, c_void]),
     "ic_refine_kmax": (c_int, [c_void, c_int, c_ll, c_void, c_void]),
+    # decoding a window of a latent: the spanned chunks alone, the crop at an offset (additive to ic_version 4)
+    "ic_codec_window_ws": (c_size, [c_int, c_ll]),
+    "ic_codec_decode_window": (c_int, [c_void, c_size, P(ICWindow), c_int, c_int, c_int, P(c_ll), c_ll, c_void, c_void,
+                                       c_ll, c_int, c_void, c_size, c_int, c_int, c_void, c_size, c_void, c_void]),
+    "ic_crop_clamp_at": (c_int, [_ACT, c_int, c_int, c_int, c_int, c_void, c_void]),
 }
 
 _lib = None
@@ -282,6 +292,7 @@ region_ops = _namespace("imgcomp_region", "scaling by a gain row per block and t
 map_ops = _namespace("imgcomp_map", "the estimated bits and the squared error of every block")
 rate_ops = _namespace("imgcomp_rate", "the sizes and the symbols of candidate streams, for coding to a byte budget")
 refine_ops = _namespace("imgcomp_refine", "the bookkeeping of encode-time latent refinement")
+window_ops = _namespace("imgcomp_window", "the decoder of a latent window and the crop at an offset")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

@@ -197,6 +197,33 @@ v0 = `_latent_gain(y)`; mu absent means that no subtraction and no addition is p
         image decides alone.  After the last evaluation the kept symbols are coded: their per-image kmax first (the
         same refusal above 2047 as `compress_each`), then `encode_symbols_seg` and `_pack_image`.
 So J_after <= J_before for every image, always, and steps = 0 gives `compress_each`'s bytes.
+
+Decoding a pixel window of a per-image stream (`Compressor2018.decompress_window`): the plan
+-------------------------------------------------------------------------------------------
+The formats above are unchanged; a window decode reads less of an "ICRP" / "ICRQ" / "ICRR" stream.  `window_plan(header,
+box, kernel, strides)` says what it reads, for the box (top, left, height, width) in pixels of the unpadded h x w image;
+a box that is empty or leaves [0, h) x [0, w) is a ValueError in front of everything else.
+    Latent window (`latent_window`).  Start from the pixel intervals [top, top + height - 1] and [left, left + width - 1]
+        and walk g_s's layers backwards: a transposed conv with kernel k, stride s and padding k // 2 maps the output
+        interval [a, b] to the input interval [ceil((a + k // 2 - (k - 1)) / s), floor((b + k // 2) / s)], clipped to
+        that level's extent after every layer (the extent of the level in front of a layer is the one behind it over s;
+        the last one is the padded latent).  For kernel 5 and strides [2, 2, 2, 2] that is at most 2 latent positions
+        beyond the box on each side.  The result is snapped outward to multiples of MAP_BLOCK // Y_DOWN = 4 latent
+        positions and clipped to the padded latent: rows [r0, r1), columns [c0, c1), whole 64 x 64 blocks of the padded
+        image, the grid of the quality maps.  GDN is pointwise, so g_s on that window alone gives, at
+        crop = (top - D r0, left - D c0) with D the product of the strides (16), the pixels of the box up to the
+        arithmetic's rounding.
+    Symbols and chunks.  y's symbols are in (h, w, c) order, so rows [r0, r1) are the symbols [r0 Wy C, r1 Wy C) and
+        those lie in the chunks [k0, k1) = [r0 Wy C // (64 R), ceil(r1 Wy C / (64 R))), each decodable alone; their bytes
+        follow from the length table.  A chunk is decoded whole (a lane's states are serial); a symbol is kept where its
+        (row, column) lies in the window.
+    What is read whole.  z is small and decoded whole; h_s runs on the whole z at batch shape 1, because its sigma bits
+        select the table rows (the rule of the per-image container); the rows and the mean of the window are taken from
+        the whole sigma and mu.
+    `byte_ranges` (with the streams' chunk-length tables given): the (begin, end) ranges of the stream a window decode
+        reads, ascending and disjoint: the header with its variable-length section, both length tables and z's payload,
+        then y's chunks k0 .. k1 - 1.  Nothing else of the stream influences the result.
+The decoded window of y_hat holds bit for bit the values `decompress_each` holds there.
 """
 import math
 import struct
@@ -826,6 +853,102 @@ def parse_region_image(data, abi, compute_dtype):
     checks of `parse_image`, and those of the levels and the map.  Nothing is launched here."""
     return _parse(data, abi, compute_dtype, _REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, REGION_FORMAT_VERSION,
                   RegionImageHeader, _check_region_image_header, var=(_map_bytes, _take_map(True)))
+
+
+# ---- decoding a pixel window of a per-image stream: what it reads (the docstring's last section)
+LATENT_SNAP = MAP_BLOCK // Y_DOWN   # a latent window is whole map blocks: multiples of 4 latent positions
+
+
+@dataclass(frozen=True)
+class WindowPlan:
+    """What a window decode of one per-image stream reads and where the box lies in what g_s returns for it."""
+    box: tuple           # (top, left, height, width), pixels of the unpadded image
+    rows: tuple          # (r0, r1): latent rows [r0, r1)
+    cols: tuple          # (c0, c1): latent columns [c0, c1)
+    crop: tuple          # (top - D r0, left - D c0): the box's corner in g_s of the latent window
+    symbols: tuple       # (r0 Wy C, r1 Wy C): the range of y's symbols that holds the rows
+    chunks: tuple        # (k0, k1): the chunks of y, at the header's R, that hold those symbols
+    byte_ranges: tuple   # ((begin, end), ...) of the stream, or None when no length tables were given
+
+    @property
+    def shape(self):
+        """(rh, rw) of the latent window."""
+        return self.rows[1] - self.rows[0], self.cols[1] - self.cols[0]
+
+
+def _walk_back(a, b, extent, kernel, strides):
+    """The closed latent interval that the pixels [a, b] of g_s's output depend on; `extent`: the latent's."""
+    down = math.prod(strides)
+    for s in reversed(strides):
+        down //= s
+        p = kernel // 2
+        a, b = -((kernel - 1 - p - a) // s), (b + p) // s     # ceil((a + p - (k - 1)) / s), floor((b + p) / s)
+        a, b = max(a, 0), min(b, extent * down - 1)
+    return a, b
+
+
+def latent_window(box, latent_hw, kernel, strides):
+    """(r0, r1, c0, c1, (crop_top, crop_left)) of the pixel box (top, left, height, width) of g_s's output for a
+    latent of `latent_hw` = (Hy, Wy) positions: the walk, the snap to LATENT_SNAP and the clip of the docstring.
+    g_s is len(strides) transposed convs of `kernel` x `kernel` taps, padding kernel // 2, with pointwise layers
+    between them.  ValueError for a box that is empty or leaves the output."""
+    kernel, strides = int(kernel), [int(s) for s in strides]
+    if kernel < 1 or not strides or min(strides) < 1:
+        raise ValueError(f"codec: no synthesis transform with kernel {kernel} and strides {strides}")
+    top, left, height, width = (int(v) for v in box)
+    D = math.prod(strides)
+    Hy, Wy = (int(v) for v in latent_hw)
+    if height < 1 or width < 1 or top < 0 or left < 0 or top + height > D * Hy or left + width > D * Wy:
+        raise ValueError(f"codec: box {(top, left, height, width)} is empty or leaves the {D * Hy} x {D * Wy} output")
+    out = []
+    for a, n, extent in ((top, height, Hy), (left, width, Wy)):
+        lo, hi = _walk_back(a, a + n - 1, extent, kernel, strides)
+        out += [lo // LATENT_SNAP * LATENT_SNAP, min(-(-(hi + 1) // LATENT_SNAP) * LATENT_SNAP, extent)]
+    return (*out, (top - D * out[0], left - D * out[2]))
+
+
+def _image_head_bytes(h):
+    """The bytes in front of the length tables of the per-image container that `h` is the header of."""
+    if isinstance(h, RegionImageHeader):
+        return _REGION_IMAGE_HEAD.size + _map_bytes(h)
+    if isinstance(h, GainedImageHeader):
+        return _GAINED_IMAGE_HEAD.size
+    if isinstance(h, ImageHeader):
+        return _IMAGE_HEAD.size
+    raise ValueError(f"codec: a window is planned on a per-image stream's header, not on a {type(h).__name__}")
+
+
+def window_plan(header, box, kernel, strides, lengths=None):
+    """The WindowPlan of the pixel box (top, left, height, width) of the stream whose parsed per-image header is
+    `header` ("ICRP", "ICRQ" or "ICRR"), for a g_s of MODEL.CONV_KERNEL `kernel` and MODEL.STRIDES `strides`.
+    `lengths` = (chunk lengths of z, of y) as the parser returns them: with them `byte_ranges` is filled in.
+    ValueError, in front of everything else, for a box that is empty or leaves [0, h) x [0, w)."""
+    try:
+        top, left, height, width = (int(v) for v in box)
+    except (TypeError, ValueError):
+        raise ValueError(f"codec: a box is (top, left, height, width), got {box!r}") from None
+    if not isinstance(header, ImageHeader):
+        raise ValueError(f"codec: a window is planned on a per-image stream's header, not on a {type(header).__name__}")
+    if height < 1 or width < 1 or top < 0 or left < 0 or top + height > header.height or left + width > header.width:
+        raise ValueError(f"codec: box {(top, left, height, width)} is empty or leaves the {header.height} x "
+                         f"{header.width} image")
+    if math.prod(int(s) for s in strides) != Y_DOWN:
+        raise ValueError(f"codec: strides {list(strides)} do not make the streams' {Y_DOWN} pixels per latent position")
+    _, C, Hy, Wy = header.y_shape
+    r0, r1, c0, c1, crop = latent_window((top, left, height, width), (Hy, Wy), kernel, strides)
+    s0, s1 = r0 * Wy * C, r1 * Wy * C
+    per = 64 * header.R
+    k0, k1 = s0 // per, -(-s1 // per)
+    ranges = None
+    if lengths is not None:
+        lens_z, lens_y = (np.asarray(l, dtype=np.int64) for l in lengths)
+        if len(lens_z) != num_chunks(header.nsym_z, header.R) or len(lens_y) != num_chunks(header.nsym_y, header.R):
+            raise ValueError("codec: the chunk-length tables are not the header's")
+        y_at = _image_head_bytes(header) + 4 * (len(lens_z) + len(lens_y)) + int(lens_z.sum())
+        ends = np.concatenate(([0], np.cumsum(lens_y)))
+        begin, end = y_at + int(ends[k0]), y_at + int(ends[k1])
+        ranges = ((0, end),) if begin == y_at else ((0, y_at), (begin, end))
+    return WindowPlan((top, left, height, width), (r0, r1), (c0, c1), crop, (s0, s1), (k0, k1), ranges)
 
 
 def split_packed_seg(packed, nseg, seg_len, R):

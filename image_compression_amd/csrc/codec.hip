@@ -18,13 +18,12 @@
 
 #include "common.h"
 #include "codec_sym.h"
+#include "codec_chunk.h"
 #include "../../include/imgcomp.h"
 
 namespace {
 
 constexpr int CODEC_KMAX = IC_CODEC_KMAX;            // 2K+1 <= 4095 counts of >= 1 fit 16 bits
-constexpr uint32_t RANS_L = 1u << 16;                // lower bound of the state interval
-constexpr size_t CODEC_LDS_BYTES = 49152;            // tables up to this size are staged in LDS
 
 // ------------------------------------------------------------------ symbolize
 // q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and max|q| by one
@@ -139,30 +138,7 @@ __global__ void codec_tables_k(const float* __restrict__ pmf, int M, uint32_t* _
 }
 
 // ------------------------------------------------------------------ rANS
-__host__ __device__ inline size_t table_bytes(int nrows, int K) { return (size_t)nrows * (2 * K + 2) * sizeof(uint32_t); }
-
-struct CodecArgs {
-  long long n;                 // symbols of the tensor
-  const unsigned char* rows;   // per-symbol table row, or null: row = global index % C
-  int C;
-  const uint32_t* cdf;         // [nrows][M + 1]
-  int nrows, K, R;
-};
-
-// the tables in LDS (LDS = true) or where they are
-template <bool LDS>
-__device__ __forceinline__ const uint32_t* stage_tables(const CodecArgs& a, uint32_t* lds) {
-  if (!LDS) return a.cdf;
-  const int words = a.nrows * (2 * a.K + 2);
-  for (int j = threadIdx.x; j < words; j += 64) lds[j] = a.cdf[j];
-  __syncthreads();
-  return lds;
-}
-
-__device__ __forceinline__ int row_of(const CodecArgs& a, long long g) {
-  const int r = a.rows ? (int)a.rows[g] : (int)(g % a.C);
-  return min(r, a.nrows - 1);
-}
+// (CodecArgs, table_bytes, stage_tables and row_of: codec_chunk.h, shared with window.hip)
 
 // One wavefront per chunk.  Steps run last to first; at a step the lanes whose state would leave
 // [2^16, 2^32) each emit their low 16 bits first.  Words are laid down from the slot's end towards its
@@ -319,46 +295,12 @@ __device__ __forceinline__ void chunk_span(const unsigned short* __restrict__ in
   *end = min(*begin + (size_t)lens[chunk] / 2, in_words);
 }
 
-// The mirror of encode_chunk.  Every read of `in` is guarded by the chunk's [begin, end); the search
-// stays inside the symbol's row.
-template <bool LDS>
-__device__ __forceinline__ void decode_chunk(const unsigned short* __restrict__ in, size_t begin, size_t end,
-                                             const CodecArgs& a, long long c0, int nc, float* __restrict__ out,
-                                             uint32_t* lds) {
-  const uint32_t* tab = stage_tables<LDS>(a, lds);
-  const int lane = threadIdx.x;
-  auto word = [&](size_t w) -> uint32_t { return w < end ? (uint32_t)in[w] : 0u; };
-
-  const int M = 2 * a.K + 1, M1 = M + 1;
-  int iters = 0;
-  while ((1 << iters) < M) ++iters;
-  const int steps = (nc + 63) >> 6;
-  uint32_t x = word(begin + 2 * lane) | (word(begin + 2 * lane + 1) << 16);
-  size_t cur = begin + 128;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-  for (int t = 0; t < steps; ++t) {
-    const int i = t * 64 + lane;
-    const bool active = i < nc;
-    bool refill = false;
-    if (active) {
-      const long long g = c0 + i;
-      const uint32_t* row = tab + (size_t)row_of(a, g) * M1;
-      const uint32_t slot = x & 0xffffu;
-      int lo = 0, hi = M - 1;  // largest j in [0, M-1] with row[j] <= slot (row[0] = 0)
-      for (int it = 0; it < iters; ++it) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (row[mid] <= slot) lo = mid; else hi = mid - 1;
-      }
-      const uint32_t start = row[lo], freq = row[lo + 1] - start;
-      x = freq * (x >> 16) + slot - start;
-      refill = x < RANS_L;
-      out[g] = (float)(lo - a.K);
-    }
-    const unsigned long long mask = __ballot(refill);
-    if (refill) x = (x << 16) | word(cur + __popcll(mask & below));
-    cur += __popcll(mask);
-  }
-}
+// (decode_chunk, the mirror of encode_chunk: codec_chunk.h)  What the decoders of whole tensors store: the symbol
+// as a float at its global index.
+struct StoreFlat {
+  float* __restrict__ out;
+  __device__ __forceinline__ void operator()(long long g, int q) const { out[g] = (float)q; }
+};
 
 template <bool LDS>
 __global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __restrict__ in, size_t in_words,
@@ -368,7 +310,7 @@ __global__ void __launch_bounds__(64) codec_decode_k(const unsigned short* __res
   chunk_span(in, in_words, nchunks, (int)blockIdx.x, &begin, &end);
   const long long per = 64ll * a.R;
   const long long c0 = (long long)blockIdx.x * per;
-  decode_chunk<LDS>(in, begin, end, a, c0, (int)min(per, a.n - c0), out, lds);
+  decode_chunk<LDS>(in, begin, end, a, c0, (int)min(per, a.n - c0), StoreFlat{out}, lds);
 }
 
 // in = the concatenation of the segments' length tables, then of their payloads, (segment, chunk) order
@@ -381,9 +323,9 @@ __global__ void __launch_bounds__(64) codec_decode_seg_k(const unsigned short* _
   int nc;
   const CodecArgs a = seg_chunk(s, &c0, &nc);
   if (table_bytes(a.nrows, a.K) <= CODEC_LDS_BYTES)
-    decode_chunk<true>(in, begin, end, a, c0, nc, out, lds);
+    decode_chunk<true>(in, begin, end, a, c0, nc, StoreFlat{out}, lds);
   else
-    decode_chunk<false>(in, begin, end, a, c0, nc, out, lds);
+    decode_chunk<false>(in, begin, end, a, c0, nc, StoreFlat{out}, lds);
 }
 
 bool codec_args_ok(long long n, const void* rows, int C, int nrows, int K, int R) {

@@ -2111,6 +2111,104 @@ Tensor refine_kmax_meta(const Tensor& sym, int64_t nseg) {
   return at::empty({nseg}, sym.options());
 }
 
+// ---------------------------------------------------------------- decoding a window of a latent (imgcomp_window)
+// windows: nine integers per window, ic_window's fields in their order (base, table, hy, wy, K, r0, c0, k0, k1);
+// spans: (begin, end) in 16-bit words of `packed` per (window, chunk).  The shapes are checked here, every
+// descriptor by the C entry point, before anything is launched.
+constexpr int64_t WINDOW_FIELDS = 9;
+
+int64_t check_window_shapes(const Tensor& packed, at::IntArrayRef windows, int64_t rh, int64_t rw, at::IntArrayRef spans,
+                            const std::optional<Tensor>& rows, const std::optional<Tensor>& mu, int64_t C,
+                            const Tensor& pool, int64_t nrows, int64_t steps) {
+  TORCH_CHECK(packed.scalar_type() == at::kByte && packed.dim() == 1 && packed.numel() > 0,
+              "imgcomp_window: packed must be a non-empty 1-D uint8 buffer");
+  TORCH_CHECK(pool.scalar_type() == at::kInt && pool.numel() > 0, "imgcomp_window: the table pool must be int32");
+  const int64_t nwin = (int64_t)windows.size() / WINDOW_FIELDS;
+  TORCH_CHECK(nwin >= 1 && nwin <= 65535 && (int64_t)windows.size() == nwin * WINDOW_FIELDS,
+              "imgcomp_window: windows holds ", WINDOW_FIELDS, " integers for each of 1 .. 65535 windows, got ",
+              windows.size());
+  TORCH_CHECK(spans.size() >= 2 && spans.size() % 2 == 0 && spans.size() / 2 <= (size_t)INT_MAX,
+              "imgcomp_window: spans holds (begin, end) per block, got ", spans.size(), " integers");
+  TORCH_CHECK(rh >= 1 && rw >= 1 && rh <= INT_MAX && rw <= INT_MAX && C >= 1 && C <= INT_MAX && nrows >= 1 &&
+                  nrows <= INT_MAX && rh * rw <= INT_MAX / C,
+              "imgcomp_window: a window is rh x rw positions of C channels, below 2^31 values");
+  TORCH_CHECK(steps >= 1 && steps <= IC_CODEC_MAXR, "imgcomp_window: steps_per_chunk in [1, ", IC_CODEC_MAXR, "]");
+  for (int64_t k = 0; k < nwin; ++k)
+    for (int64_t f = 2; f < WINDOW_FIELDS; ++f)
+      TORCH_CHECK(windows[k * WINDOW_FIELDS + f] >= INT_MIN && windows[k * WINDOW_FIELDS + f] <= INT_MAX,
+                  "imgcomp_window: field ", f, " of window ", k, " is not an int");
+  const bool hr = rows.has_value() && rows->defined(), hm = mu.has_value() && mu->defined();
+  TORCH_CHECK(!hr || rows->scalar_type() == at::kByte, "imgcomp_window: rows must be uint8");
+  TORCH_CHECK(!hm || mu->scalar_type() == at::kFloat, "imgcomp_window: mu must be float32");
+  TORCH_CHECK(!hr || !hm || rows->numel() == mu->numel(), "imgcomp_window: rows and mu must hold one value per symbol");
+  return nwin;
+}
+
+Tensor window_decode(const Tensor& packed, at::IntArrayRef windows, int64_t rh, int64_t rw, at::IntArrayRef spans,
+                     const std::optional<Tensor>& rows, const std::optional<Tensor>& mu, int64_t C, const Tensor& pool,
+                     int64_t nrows, int64_t steps) {
+  const int64_t nwin = check_window_shapes(packed, windows, rh, rw, spans, rows, mu, C, pool, nrows, steps);
+  check_codec(packed, at::kByte, "packed");
+  check_codec(pool, at::kInt, "table pool");
+  const bool hr = rows.has_value() && rows->defined(), hm = mu.has_value() && mu->defined();
+  if (hr) check_codec(*rows, at::kByte, "rows");
+  if (hm) {
+    check_dense(*mu, "mu");
+    TORCH_CHECK(mu->is_contiguous(), "imgcomp_window: mu must be contiguous");
+  }
+  for (const Tensor* t : {&pool, hr ? &*rows : &packed, hm ? &*mu : &packed})
+    TORCH_CHECK(t->device() == packed.device(), "imgcomp_window: every operand must be on packed's device");
+  TORCH_CHECK(((uintptr_t)packed.data_ptr() & 1) == 0, "imgcomp_window: packed buffer must be 2-byte aligned");
+  std::vector<ic_window> win((size_t)nwin);
+  for (int64_t k = 0; k < nwin; ++k) {
+    const int64_t* f = windows.data() + k * WINDOW_FIELDS;
+    win[(size_t)k] = ic_window{f[0], f[1], (int)f[2], (int)f[3], (int)f[4], (int)f[5], (int)f[6], (int)f[7], (int)f[8]};
+  }
+  const std::vector<long long> sp(spans.begin(), spans.end());
+  const int64_t nblocks = (int64_t)sp.size() / 2;
+  // with neither rows nor a mean nothing is indexed by a symbol's number: no bound on the segments' ends
+  const int64_t nsym = hr ? rows->numel() : (hm ? mu->numel() : INT64_MAX);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(packed.device());
+  const size_t wsb = ic_codec_window_ws((int)nwin, nblocks);
+  Tensor ws = at::empty({(int64_t)std::max<size_t>(wsb, 8) / 8 + 1}, packed.options().dtype(at::kLong));
+  Tensor out = at::empty({nwin, rh, rw, C}, packed.options().dtype(at::kFloat));
+  check_rc(ic_codec_decode_window(packed.data_ptr(), (size_t)packed.numel(), win.data(), (int)nwin, (int)rh, (int)rw,
+                                  sp.data(), nblocks, hr ? rows->data_ptr<unsigned char>() : nullptr,
+                                  hm ? mu->data_ptr<float>() : nullptr, nsym, (int)C,
+                                  (const unsigned int*)pool.data_ptr<int>(), (size_t)pool.numel(), (int)nrows, (int)steps,
+                                  ws.data_ptr(), (size_t)ws.numel() * 8, out.data_ptr<float>(), stream_of(packed)),
+           "codec_decode_window");
+  return out;
+}
+
+void check_crop_at(const Tensor& x, int64_t top, int64_t left, int64_t h, int64_t w) {
+  TORCH_CHECK(x.dim() == 4 && x.numel() > 0 && h >= 1 && w >= 1 && top >= 0 && left >= 0 && h <= x.size(2) &&
+                  w <= x.size(3) && top <= x.size(2) - h && left <= x.size(3) - w,
+              "imgcomp_window: crop_clamp_at takes (N, C, H, W) and a rectangle inside H x W, got ", x.sizes(), " -> ", h,
+              " x ", w, " at (", top, ", ", left, ")");
+}
+
+Tensor window_crop_clamp_at(const Tensor& x, int64_t top, int64_t left, int64_t h, int64_t w) {
+  check_operand(x, "x");
+  check_crop_at(x, top, left, h, w);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor y = at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
+  const ic_act ax = act_of(x);
+  check_rc(ic_crop_clamp_at(&ax, (int)top, (int)left, (int)h, (int)w, y.data_ptr<float>(), stream_of(x)), "crop_clamp_at");
+  return y;
+}
+
+Tensor window_decode_meta(const Tensor& packed, at::IntArrayRef windows, int64_t rh, int64_t rw, at::IntArrayRef spans,
+                          const std::optional<Tensor>& rows, const std::optional<Tensor>& mu, int64_t C, const Tensor& pool,
+                          int64_t nrows, int64_t steps) {
+  const int64_t nwin = check_window_shapes(packed, windows, rh, rw, spans, rows, mu, C, pool, nrows, steps);
+  return at::empty({nwin, rh, rw, C}, packed.options().dtype(at::kFloat));
+}
+Tensor window_crop_clamp_at_meta(const Tensor& x, int64_t top, int64_t left, int64_t h, int64_t w) {
+  check_crop_at(x, top, left, h, w);
+  return at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -2523,4 +2621,22 @@ TORCH_LIBRARY_IMPL(imgcomp_refine, Meta, m) {
   m.impl("objective", refine_objective_meta);
   m.impl("keep", refine_keep_meta);
   m.impl("kmax", refine_kmax_meta);
+}
+
+// Decoding a pixel window of a per-image stream (Compressor2018.decompress_window): additive, in a namespace of its
+// own.  Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_window, m) {
+  m.def("decode(Tensor packed, int[] windows, int rh, int rw, int[] spans, Tensor? rows, Tensor? mu, int channels, "
+        "Tensor pool, int nrows, int steps_per_chunk) -> Tensor");
+  m.def("crop_clamp_at(Tensor x, int top, int left, int height, int width) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_window, CUDA, m) {
+  m.impl("decode", window_decode);
+  m.impl("crop_clamp_at", window_crop_clamp_at);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_window, Meta, m) {
+  m.impl("decode", window_decode_meta);
+  m.impl("crop_clamp_at", window_crop_clamp_at_meta);
 }

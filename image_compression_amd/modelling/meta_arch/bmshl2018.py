@@ -19,7 +19,8 @@ from ... import noise as _noise
 from ...functional import (AbsFn, CELossFn, NonNegFn, NonNegMultiFn, RoundThroughFn, _match, _to_last, block_bits,
                            block_sse, conditional_likelihood, factorized, refine_dist_grad, refine_keep, refine_kmax,
                            refine_objective, refine_update, route_weight_gradients)
-from ..blocks.entropy_model import symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor
+from ..blocks.entropy_model import (symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor,
+                                    table_pool)
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
@@ -120,6 +121,8 @@ class Compressor2018(nn.Module):
         self.distortion_loss_fns = get_loss_dict(cfg, cfg.MODEL.LOSS.DISTORTION_LOSS_NAMES)
         self.distortion_loss_weight = cfg.MODEL.LOSS.DISTORTION_LOSS_WEIGHT
         self.loss_names = ["y_entropy", "z_entropy", "bpp"] + list(self.distortion_loss_fns.keys())
+        # g_s's taps and strides: what a pixel of the output depends on (decompress_window)
+        self._synthesis_geometry = (int(cfg.MODEL.CONV_KERNEL), tuple(int(s) for s in cfg.MODEL.STRIDES))
         # the hyperprior branch (h_a, factorized model, h_s, the y likelihood) on a second
         # stream, concurrent with the synthesis transform (see forward)
         self.concurrent_hyperprior = True
@@ -462,6 +465,106 @@ class Compressor2018(nn.Module):
                                                           [h.kmax_y for h in hs], R, mean=mean))
             for m, img in zip(idx, self._reconstruct_each(y_hat, hs)):
                 out[m] = img
+        return out
+
+    # ---- a pixel window of a per-image stream: only the chunks that hold its latent rows are decoded and g_s runs on the
+    # latent window alone (codec.py states the plan).  The streams are `compress_each`'s, unchanged.
+    window_refusal = None    # a model whose streams do not map a band of latent rows to a chunk range says why here
+
+    def _begin_window_decode(self, hs, plans):
+        """`_begin_decode` for a group of latent windows, one header and one plan per window: what `_latent_ungain`
+        needs to act on the windows."""
+        self._begin_decode(hs)
+
+    @torch.no_grad()
+    def _window_latents(self, streams, boxes):
+        """(plans, groups): the WindowPlan of every box and, per group of windows that share a latent shape and a
+        chunk size, ([m], what g_s reads for them, (len([m]), C, rh, rw)).  Everything is parsed and planned
+        before any launch; a bytes object given more than once is parsed, z-decoded and passed through h_s once."""
+        who = "decompress_window"
+        if self.window_refusal:
+            raise ValueError(f"{who}: {self.window_refusal}")
+        self._codable_each()
+        em, cm = self.entropy_model, self.conditional_model
+        streams, boxes = list(streams), list(boxes)
+        if len(streams) != len(boxes):
+            raise ValueError(f"{who}: {len(streams)} streams for {len(boxes)} boxes")
+        kernel, strides = self._synthesis_geometry
+        parsed, owner, seen = [], [], {}
+        for m, d in enumerate(streams):
+            if id(d) not in seen:     # the same object, not an equal one: `streams` keeps every object alive
+                seen[id(d)] = len(parsed)
+                parsed.append(self._parse_image(d, *self._build_id()))
+                self._check_stream(parsed[-1][0], who, f"stream {m}")
+            owner.append(seen[id(d)])
+        plans = []
+        for m, s in enumerate(owner):
+            h, lz, ly = parsed[s][:3]
+            try:
+                plans.append(_codec.window_plan(h, boxes[m], kernel, strides, lengths=(lz, ly)))
+            except ValueError as e:
+                raise ValueError(f"{who}: box {m}: {e}") from None
+        # per distinct stream: z whole, h_s on the whole z at batch shape 1 (its sigma bits select the table rows)
+        prior = []
+        for h, lz, _ly, pz, _py in parsed:
+            self._begin_decode([h])
+            z_hat = em.decompress_seg([pz], h.z_shape, [lz], [h.kmax_z], h.R)
+            sigma, mean = self._prior_each(self._hyper_ungain(z_hat))
+            if tuple(sigma.shape) != h.y_shape:
+                raise ValueError(f"{who}: the model's sigma {tuple(sigma.shape)} is not the stream's latent shape "
+                                 f"{h.y_shape}")
+            prior.append((cm.scale_rows(sigma), None if mean is None else _to_last(mean).reshape(-1)))
+        groups = {}
+        for m, s in enumerate(owner):
+            groups.setdefault((*plans[m].shape, parsed[s][0].latent_channels, parsed[s][0].R), []).append(m)
+        out = []
+        for (rh, rw, C, R), idx in groups.items():
+            hs = [parsed[owner[m]][0] for m in idx]
+            used = sorted({owner[m] for m in idx})
+            base, at = {}, 0
+            for s in used:     # the rows (and the means) of the group's streams back to back
+                base[s] = at
+                at += prior[s][0].numel()
+            rows = prior[used[0]][0] if len(used) == 1 else torch.cat([prior[s][0] for s in used])
+            mu = None
+            if prior[used[0]][1] is not None:
+                mu = prior[used[0]][1] if len(used) == 1 else torch.cat([prior[s][1] for s in used])
+            pool, nrows, ks, offs = table_pool(lambda K: cm.tables(K, rows.device), [h.kmax_y for h in hs])
+            # the payload of the spanned chunks alone, a chunk range that several windows share once
+            parts, where, words, windows, spans = [], {}, 0, [], []
+            ends_of = {s: np.concatenate(([0], np.cumsum(parsed[s][2], dtype=np.int64))) for s in used}
+            for m, h, K, off in zip(idx, hs, ks, offs):
+                s, (k0, k1) = owner[m], plans[m].chunks
+                ends = ends_of[s]
+                if (s, k0, k1) not in where:
+                    where[s, k0, k1] = words
+                    parts.append(parsed[s][4][int(ends[k0]):int(ends[k1])])
+                    words += len(parts[-1]) // 2
+                first = where[s, k0, k1] - int(ends[k0]) // 2
+                spans += [first + int(e) // 2 for k in range(k0, k1) for e in (ends[k], ends[k + 1])]
+                _, _, Hy, Wy = h.y_shape
+                windows += [base[s], off, Hy, Wy, K, plans[m].rows[0], plans[m].cols[0], k0, k1]
+            buf = torch.from_numpy(np.frombuffer(b"".join(parts), dtype=np.uint8).copy()).to(rows.device)
+            flat = _lib.window_ops().decode(buf, windows, rh, rw, spans, rows, mu, C, pool, nrows, R)
+            self._begin_window_decode(hs, [plans[m] for m in idx])
+            out.append((idx, self._latent_ungain(symbols_as_tensor(flat, (len(idx), C, rh, rw)))))
+        return plans, out
+
+    @torch.no_grad()
+    def decompress_window(self, streams, boxes):
+        """streams[m]: bytes from `compress_each`, `compress_each_to` or `compress_each_refined`, unchanged;
+        boxes[m] = (top, left, height, width) in pixels of that image -> a list of tensors (1, 3, height_m, width_m):
+        the box of what `decompress_each` returns for the stream, up to the arithmetic's rounding (g_s runs on another
+        shape), from the chunks of y that hold the box's latent rows and g_s on the latent window alone.  z and h_s are
+        decoded and run whole, once per bytes object: give the tiles of one image the same object.  Windows that
+        share a latent shape and a chunk size are decoded by one launch and pass g_s as one batch."""
+        plans, groups = self._window_latents(streams, boxes)
+        out = [None] * len(plans)
+        for idx, y_hat in groups:
+            x = self.synthesis_transform(y_hat)
+            for k, m in enumerate(idx):
+                _, _, height, width = plans[m].box
+                out[m] = _lib.window_ops().crop_clamp_at(x[k:k + 1], *plans[m].crop, height, width)
         return out
 
     # ---- encode-time latent refinement: lower R + lambda D for this image, same decoder (codec.py states the rule)

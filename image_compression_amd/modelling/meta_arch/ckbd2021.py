@@ -57,6 +57,9 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
 
     refine_refusal = ("CheckerboardCompressor2018 is not covered: the non-anchors' (sigma, mu) depend on y, so moving y "
                       "moves the decoder's inputs")
+    window_refusal = ("CheckerboardCompressor2018 is not covered: y is coded as two gathered halves, anchors and "
+                      "non-anchors, so a band of latent rows is not a range of chunks, and the non-anchors' (sigma, mu) "
+                      "need the anchors around them")
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -212,3 +212,10 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
     def _begin_decode(self, headers):
         codes = headers[0].codes if len(headers) == 1 and headers[0].codes.ndim == 3 else np.stack([h.codes for h in headers])
         self._use_map(codes, next(self.parameters()).device)
+
+    def _begin_window_decode(self, hs, plans):
+        """Every window's own blocks of its stream's map: a latent window is whole blocks (codec.LATENT_SNAP), and a
+        gain row is a function of its code alone, so the cropped map gives the window the gains of the whole one."""
+        n = _codec.LATENT_SNAP
+        codes = np.stack([h.codes[p.rows[0] // n:p.rows[1] // n, p.cols[0] // n:p.cols[1] // n] for h, p in zip(hs, plans)])
+        self._use_map(codes, next(self.parameters()).device)

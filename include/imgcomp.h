@@ -735,6 +735,45 @@ int ic_refine_keep(const int* sym, int* best_sym, const double* obj, double* bes
  * atomicMax per block after a memset on the stream */
 int ic_refine_kmax(const int* sym, int N, long long len, int* kmax, void* stream);
 
+/* ---- decoding a window of a latent (additive to version 4; Compressor2018.decompress_window).  The chunks of a
+ *      segment's bitstream are decodable alone and its symbols lie in (row, column, channel) order, so a band of rows
+ *      is a range of chunks: only those are decoded, and only the symbols inside the window are stored. ---- */
+/* One window: a rectangle of latent positions of one segment (an image's y). */
+typedef struct ic_window {
+  long long base;  /* index of the segment's first symbol in rows / mu */
+  long long table; /* word offset of the segment's table in the pool */
+  int hy, wy;      /* the segment is hy rows of wy positions of C channels: hy * wy * C symbols, below 2^31 */
+  int K;           /* the segment's K */
+  int r0, c0;      /* the window's first row and column; it ends at r0 + rh <= hy and c0 + rw <= wy */
+  int k0, k1;      /* the chunks [k0, k1) of the segment, k1 <= its chunk count, that the call brings: they must
+                      hold every symbol of rows [r0, r0 + rh) */
+} ic_window;
+/* bytes of the device workspace of ic_codec_decode_window (its descriptors); 0 for counts below 1 */
+size_t ic_codec_window_ws(int nwin, long long nblocks);
+/* Decodes nwin (1 .. 65535) windows of one latent shape rh x rw in one launch, block = one wavefront = one
+ * (window, chunk) pair in (window, chunk) order: nblocks = the sum of k1 - k0.  in: 16-bit words, in_bytes of them
+ * counted in bytes; spans (host): for every block the (begin, end) of its chunk in `in`, in words, 0 <= begin <= end
+ * <= in_bytes / 2: the caller brings the payload of the spanned chunks alone and no block reads a length table.  A
+ * chunk is decoded by the arithmetic of ic_codec_decode_seg with its guards (no read outside [begin, end), no search
+ * outside the symbol's row), the table staged in LDS where nrows * (2K + 2) * 4 <= 48 KiB, the row of symbol g (its
+ * index in rows: base + its index in the segment) rows[g], or g % C where rows is NULL (then base % C == 0 and
+ * C <= nrows).  Every symbol of a chunk is decoded, the states being serial; the symbol q at (row, column, channel)
+ * is stored where the window holds it:
+ *     out[window][row - r0][column - c0][channel] = (float)q, or with mu: (float)q + mu[g], ic_add_mean's addition
+ * out: (nwin, rh, rw, C) dense, every element written.  rows and mu, where given, hold nsym elements.  ws: 8-byte aligned device
+ * memory of ic_codec_window_ws bytes (IC_ERR_WORKSPACE below that), written by one copy from host arrays that are
+ * consumed before the call returns.  Every descriptor is checked before anything touches the device -- the window
+ * inside its segment, the chunk range inside the segment's chunk count and over the window's rows, the spans inside
+ * the buffer, K and the table inside the pool, the segment inside rows / mu -- IC_ERR_ARG otherwise: they come from
+ * untrusted streams.  Neither allocates device memory nor waits for its stream. */
+int ic_codec_decode_window(const void* in, size_t in_bytes, const ic_window* win, int nwin, int rh, int rw,
+                           const long long* spans, long long nblocks, const unsigned char* rows, const float* mu,
+                           long long nsym, int C, const unsigned int* pool, size_t pool_words, int nrows,
+                           int steps_per_chunk, void* ws, size_t ws_bytes, float* out, void* stream);
+/* ic_crop_clamp at an offset: y (N, C, h, w dense) = min(max(x, 0), 1) as ic_crop_clamp computes it, of
+ * x[:, :, top : top + h, left : left + w] (any strides >= 0); one pass, bit for bit the two bounds then the slice */
+int ic_crop_clamp_at(const ic_act* x, int top, int left, int h, int w, float* y, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
