@@ -266,6 +266,10 @@ SIGNATURES = {
     "ic_codec_decode_window": (c_int, [c_void, c_size, P(ICWindow), c_int, c_int, c_int, P(c_ll), c_ll, c_void, c_void,
                                        c_ll, c_int, c_void, c_size, c_int, c_int, c_void, c_size, c_void, c_void]),
     "ic_crop_clamp_at": (c_int, [_ACT, c_int, c_int, c_int, c_int, c_void, c_void]),
+    # transcoding in the latent domain: y's symbols at other qualities from a stream's decoded integers (additive to
+    # ic_version 4)
+    "ic_requant_seg": (c_int, [c_void, c_void, c_ll, c_ll, c_int, c_void, c_void, c_void, c_int, P(c_int), c_void,
+                               c_void, c_void, P(c_int), c_void]),
 }
 
 _lib = None
@@ -293,6 +297,7 @@ map_ops = _namespace("imgcomp_map", "the estimated bits and the squared error of
 rate_ops = _namespace("imgcomp_rate", "the sizes and the symbols of candidate streams, for coding to a byte budget")
 refine_ops = _namespace("imgcomp_refine", "the bookkeeping of encode-time latent refinement")
 window_ops = _namespace("imgcomp_window", "the decoder of a latent window and the crop at an offset")
+transcode_ops = _namespace("imgcomp_transcode", "y's symbols at other qualities from a stream's decoded integers")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

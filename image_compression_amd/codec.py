@@ -224,7 +224,41 @@ a box that is empty or leaves [0, h) x [0, w) is a ValueError in front of everyt
         reads, ascending and disjoint: the header with its variable-length section, both length tables and z's payload,
         then y's chunks k0 .. k1 - 1.  Nothing else of the stream influences the result.
 The decoded window of y_hat holds bit for bit the values `decompress_each` holds there.
+
+Transcoding in the latent domain (`Compressor2018.transcode_each`, `GainedMeanScaleCompressor2018.transcode_each_to`)
+---------------------------------------------------------------------------------------------------------------------
+A per-image stream ("ICRP" / "ICRQ" / "ICRR") becomes another stream of the same model without passing through pixels:
+neither g_a nor g_s runs.  The formats above are unchanged.
+    Re-chunking.  The symbols of z and of y are decoded and coded again at another R = steps_per_chunk; y is decoded
+        without its mean (the residual integers), under the rows of sigma = h_s(z_hat) evaluated once.  The output's
+        header is the parsed one with R replaced (`transcoded_header`): kmax_z, kmax_y, the quality and the map stay.
+        The result is bit for bit the stream `compress_each` writes for the same image at that R.
+    Requantization ("ICRQ" only).  From the stream's quality q1 to a quality q2 != q1; the gain vectors
+        (g_y, g_y', g_z, g_z') at q1 and at q2 are the gain-vector rule's, from the stored float32 values.  Every *, +, -
+        below is one float32 operation, rounded once, never contracted with another; (sigma, mu) = h_s(.) is evaluated
+        on one stream at a time (batch shape 1), as everywhere in the per-image streams:
+            k_z1 = the decoded integers of z          z_hat1 = k_z1 * g_z'(q1)       (sigma1, mu1) = h_s(z_hat1)
+            k_z2 = symbol_of(z_hat1 * g_z(q2))        z_hat2 = k_z2 * g_z'(q2)       (sigma2, mu2) = h_s(z_hat2)
+            r1   = the decoded integers of y (the residual about mu1)
+            k_y2 = symbol_of(((r1 + mu1) * g_y'(q1)) * g_y(q2) - mu2)
+        (r1 + mu1) * g_y'(q1) is exactly the y_hat that g_s would read.  y is coded with the rows of sigma2 and the tables
+        of its own K; the header is the parsed one with quality = q2 and kmax_z, kmax_y, R replaced.  A symbol beyond
+        KMAX_LIMIT is a ValueError naming the stream.  At q2 == q1 nothing is requantized (the stream is returned, or
+        only re-chunked): g' * g is not 1 for learnt tables, so an equal quality must not cost a generation.
+    To a byte budget (`transcode_each_to`).  A stream is first re-chunked where another R is asked; one that then
+        holds at most its budget is the result, at its own quality q1.  Otherwise the search rule of
+        `compress_each_to` above runs on the sizes the coder reports for the requantized candidates, with two
+        differences:
+            round 1 searches `transcode_grid(S, Q, q1)` = [q for q in budget_grid(S, Q) if q < q1]: transcoding upwards
+                buys bytes and no quality.  An empty list (q1 = 0) is a miss, as is a round 1 of which nothing fits;
+            what is measured for the stream starts as `transcode_measured(q1, len(stream))` = {q1: len(stream)}, so that
+                `budget_next` / `budget_refine` refine between the top grid point below q1 and q1, strictly inside.
+        A miss is a `BudgetError` (strict) in front of the packing of any requantized stream -- for a stream at q1 = 0
+        that already has the target R, in front of any launch; one that has to be re-chunked is judged at its
+        re-chunked length, which may fit -- or the stream at quality 0 (for q1 = 0 the stream itself, re-chunked where
+        asked): the one result that may exceed its budget.
 """
+import dataclasses
 import math
 import struct
 from dataclasses import dataclass
@@ -721,6 +755,35 @@ def budget_next(measured, chosen):
     """The next larger quality than `chosen` among `measured`, or None."""
     above = [q for q in measured if q > chosen]
     return min(above) if above else None
+
+
+def transcode_grid(S, Q, q1):
+    """Round 1 of `transcode_each_to` for a stream coded at quality q1: the qualities of `budget_grid(S, Q)` strictly
+    below q1, ascending.  Empty at q1 = 0."""
+    q1 = float(q1)
+    if not 0.0 <= q1 <= _check_levels(S) - 1:    # NaN included
+        raise ValueError(f"codec: quality {q1!r} is outside [0, {S - 1}]")
+    return [q for q in budget_grid(S, Q) if q < q1]
+
+
+def transcode_measured(q1, size):
+    """What is measured for a stream of `size` bytes coded at quality q1 before `transcode_each_to` measures anything:
+    the stream itself, the upper end of every later refinement."""
+    if isinstance(size, bool) or not isinstance(size, (int, np.integer)) or size < 1:
+        raise ValueError(f"codec: a stream's size is a positive int, a number of bytes, got {size!r}")
+    return {float(q1): int(size)}
+
+
+def transcoded_header(h, **changes):
+    """The header of a transcoded per-image stream: the parsed header `h` with `changes` among R, quality, kmax_z and
+    kmax_y replaced; everything else, a region stream's map included, is the parsed stream's."""
+    if not isinstance(h, ImageHeader):
+        raise ValueError(f"codec: a per-image stream's header is transcoded, not a {type(h).__name__}")
+    allowed = {"R", "kmax_z", "kmax_y"} | ({"quality"} if isinstance(h, GainedImageHeader) else set())
+    if not set(changes) <= allowed:
+        raise ValueError(f"codec: transcoding a {type(h).__name__} replaces {sorted(allowed)}, not "
+                         f"{sorted(set(changes) - allowed)}")
+    return dataclasses.replace(h, **changes)
 
 
 def image_stream_bytes(fixed, *lens):

@@ -1948,6 +1948,60 @@ std::tuple<Tensor, std::vector<int64_t>> rate_gain_symbolize_seg_meta(const Tens
   return {symbols_out(mu), std::vector<int64_t>(img.size(), 0)};
 }
 
+// ---------------------------------------------------------------- transcoding in the latent domain (imgcomp_transcode)
+// r, mu1 (N, *, C) contiguous, read in place; a (N, C); b (M, C); mu2: the M targets' means back to back, each an image
+// of r's size; img: the source of every target
+void check_transcode_shapes(const Tensor& r, const Tensor& mu1, const Tensor& a, const Tensor& b, const Tensor& mu2,
+                            at::IntArrayRef img) {
+  const int64_t M = (int64_t)img.size();
+  TORCH_CHECK(r.dim() >= 2 && r.numel() > 0, "imgcomp_transcode: r must be a non-empty (N, *, C) tensor, got ", r.sizes());
+  TORCH_CHECK(mu1.sizes() == r.sizes(), "imgcomp_transcode: mu1 ", mu1.sizes(), " must have r's shape ", r.sizes());
+  TORCH_CHECK(a.dim() == 2 && a.size(0) == r.size(0) && a.size(1) == r.size(-1), "imgcomp_transcode: the source gains ",
+              a.sizes(), " must be (", r.size(0), " sources, ", r.size(-1), ")");
+  TORCH_CHECK(M >= 1 && M <= 65535 && b.dim() == 2 && b.size(0) == M && b.size(1) == r.size(-1),
+              "imgcomp_transcode: the target gains ", b.sizes(), " must be (", M, " targets, ", r.size(-1), ")");
+  TORCH_CHECK(mu2.numel() == M * (r.numel() / r.size(0)), "imgcomp_transcode: mu2 (", mu2.numel(), " values) must hold ",
+              M, " images of ", r.numel() / r.size(0), " values");
+}
+
+std::tuple<Tensor, std::vector<int64_t>> transcode_requant_seg(const Tensor& r, const Tensor& mu1, const Tensor& a,
+                                                               const Tensor& b, const Tensor& mu2, at::IntArrayRef img) {
+  const std::pair<const Tensor*, const char*> operands[] = {{&r, "r"}, {&mu1, "mu1"}, {&a, "a"}, {&b, "b"}, {&mu2, "mu2"}};
+  for (const auto& [t, what] : operands) check_operand(*t, what);
+  check_transcode_shapes(r, mu1, a, b, mu2, img);
+  for (const auto& [t, what] : operands) {
+    TORCH_CHECK(t->is_contiguous(), "imgcomp_transcode: ", what, " must be contiguous");
+    TORCH_CHECK(t->device() == r.device(), "imgcomp_transcode: every operand must be on r's device");
+  }
+  const int64_t M = (int64_t)img.size(), N = r.size(0), C = r.size(-1);
+  TORCH_CHECK(N <= 65535 && C <= INT_MAX, "imgcomp_transcode: r is too large: ", r.sizes());
+  std::vector<int> im;
+  for (int64_t m = 0; m < M; ++m) {
+    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_transcode: target ", m, " names source ", img[m], " of ", N);
+    im.push_back((int)img[m]);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(r.device());
+  Tensor sym = symbols_out(mu2);
+  Tensor kd = at::empty({2 * M}, r.options().dtype(at::kInt));   // the maxima, then the sources
+  std::vector<int> kmax((size_t)M, 0);
+  const int rc = ic_requant_seg(r.data_ptr<float>(), mu1.data_ptr<float>(), N, r.numel() / N / C, (int)C,
+                                a.data_ptr<float>(), b.data_ptr<float>(), mu2.data_ptr<float>(), (int)M, im.data(),
+                                kd.data_ptr<int>() + M, sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(r));
+  if (rc == IC_ERR_ARG)
+    for (int64_t m = 0; m < M; ++m)
+      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_transcode: target ", m, " (source ", img[m],
+                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "requant_seg");
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
+std::tuple<Tensor, std::vector<int64_t>> transcode_requant_seg_meta(const Tensor& r, const Tensor& mu1, const Tensor& a,
+                                                                    const Tensor& b, const Tensor& mu2,
+                                                                    at::IntArrayRef img) {
+  check_transcode_shapes(r, mu1, a, b, mu2, img);
+  return {symbols_out(mu2), std::vector<int64_t>(img.size(), 0)};
+}
+
 // ---------------------------------------------------------------- encode-time latent refinement (imgcomp_refine)
 // The latent is (N, *, C) contiguous (channels-last storage); v, m and u are updated in place.  Nothing here copies to
 // the host or waits for the stream.  Inference only: no autograd node.
@@ -2640,3 +2694,13 @@ TORCH_LIBRARY_IMPL(imgcomp_window, Meta, m) {
   m.impl("decode", window_decode_meta);
   m.impl("crop_clamp_at", window_crop_clamp_at_meta);
 }
+
+// Transcoding in the latent domain (Compressor2018.transcode_each, GainedMeanScaleCompressor2018.transcode_each_to):
+// additive, in a namespace of its own.  Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_transcode, m) {
+  m.def("requant_seg(Tensor r, Tensor mu1, Tensor a, Tensor b, Tensor mu2, int[] img) -> (Tensor, int[])");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_transcode, CUDA, m) { m.impl("requant_seg", transcode_requant_seg); }
+
+TORCH_LIBRARY_IMPL(imgcomp_transcode, Meta, m) { m.impl("requant_seg", transcode_requant_seg_meta); }

@@ -1012,6 +1012,33 @@ def gain_symbolize_seg(y, g, mean, img):
     return sym, [int(k) for k in kmax]
 
 
+# ============================================================== transcoding in the latent domain
+def requant_seg(r, mu1, a, b, mu2, img):
+    """The symbols of y at M target qualities from N decoded streams: r (N, C, *) the decoder's float integers of y,
+    mu1 (N, C, *) their means, a (N, C) the sources' inverse gains; target m is source img[m] under the gain row b[m]
+    of b (M, C), coded about mu2[m] of mu2 (M, C, *) -> (int32 rint(((r + mu1) * a) * b - mu2) of the M targets back
+    to back, each in (*, c) order, [kmax of target m]), every operation one fp32 operation.  Bit for bit `add_mean`,
+    `channel_scale` twice and `symbolize_mean_seg` on the gathered batch, which is never formed
+    (torch.ops.imgcomp_transcode.requant_seg; the requantization rule of codec.py).  Inference only; ValueError naming
+    the target whose symbols exceed the coder's limit."""
+    _lib.require_device(r, mu1, a, b, mu2)
+    img = [int(i) for i in img]
+    if r.dim() < 2 or tuple(mu1.shape) != tuple(r.shape):
+        raise ValueError(f"the mean {tuple(mu1.shape)} must have the shape of the integers {tuple(r.shape)}")
+    if a.dim() != 2 or tuple(a.shape) != (r.shape[0], r.shape[1]):
+        raise ValueError(f"the source gains {tuple(a.shape)} must be ({r.shape[0]} sources, C) for a tensor of shape "
+                         f"{tuple(r.shape)}")
+    if b.dim() != 2 or tuple(b.shape) != (len(img), r.shape[1]):
+        raise ValueError(f"the target gains {tuple(b.shape)} must be ({len(img)} targets, C) for a tensor of shape "
+                         f"{tuple(r.shape)}")
+    if tuple(mu2.shape) != (len(img), *r.shape[1:]):
+        raise ValueError(f"the mean {tuple(mu2.shape)} must hold {len(img)} targets of shape {tuple(r.shape[1:])}")
+    _inference_only("requant_seg", r=r, mu1=mu1, a=a, b=b, mu2=mu2)
+    sym, kmax = _lib.transcode_ops().requant_seg(_to_last(r.detach()), _to_last(mu1.detach()), a.detach().contiguous(),
+                                                 b.detach().contiguous(), _to_last(mu2.detach()), img)
+    return sym, [int(k) for k in kmax]
+
+
 # ============================================================== region-of-interest coding
 def _block_map(idx, device):
     """A block map as the kernels take it: contiguous uint8 on the device."""

@@ -19,8 +19,8 @@ from ... import noise as _noise
 from ...functional import (AbsFn, CELossFn, NonNegFn, NonNegMultiFn, RoundThroughFn, _match, _to_last, block_bits,
                            block_sse, conditional_likelihood, factorized, refine_dist_grad, refine_keep, refine_kmax,
                            refine_objective, refine_update, route_weight_gradients)
-from ..blocks.entropy_model import (symbolize, symbolize_mean, symbolize_mean_seg, symbolize_seg, symbols_as_tensor,
-                                    table_pool)
+from ..blocks.entropy_model import (_decode_seg, _encode_seg, symbolize, symbolize_mean, symbolize_mean_seg,
+                                    symbolize_seg, symbols_as_tensor, table_pool)
 from ..blocks import (ENTROPY_MODEL_REGISTRY, AnalysisTransform, HyperpriorAnalysisTransform,
                       HyperpriorSynthesisTransform, SynthesisTransform)
 from ..layers import LowerBound, UpperBound
@@ -565,6 +565,110 @@ class Compressor2018(nn.Module):
             for k, m in enumerate(idx):
                 _, _, height, width = plans[m].box
                 out[m] = _lib.window_ops().crop_clamp_at(x[k:k + 1], *plans[m].crop, height, width)
+        return out
+
+    # ---- transcoding in the latent domain: a stream to another stream of this model without g_a or g_s (codec.py states
+    # the rules).  Re-chunking here; the gained model adds requantization to another quality and to a byte budget.
+    transcode_refusal = None    # a model whose streams are not one bitstream of z and one of y says why here
+
+    def _transcode_qualities(self, qualities, M, who):
+        """The float32 target quality of every one of M streams; here a refusal: this model codes at one rate."""
+        raise ValueError(f"{who}: {type(self).__name__} codes at one rate: `qualities` needs the gain units of "
+                         "GainedMeanScaleCompressor2018; leave it None to re-chunk")
+
+    def _transcode_parse(self, streams, steps_per_chunk, who, qualities=None):
+        """(streams as a list, [(header, lens_z, lens_y, payload_z, payload_y)], the target qualities or None): every
+        refusal and every check of the arguments and the streams, in front of any launch."""
+        if self.transcode_refusal:
+            raise ValueError(f"{who}: {self.transcode_refusal}")
+        self._codable_each()
+        if isinstance(streams, (bytes, bytearray, memoryview, str)):
+            raise ValueError(f"{who}: `streams` is a list of per-image streams, not one {type(streams).__name__}")
+        streams = list(streams)
+        R = steps_per_chunk
+        if R is not None and (isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 1 <= R <= _codec.MAX_STEPS):
+            raise ValueError(f"{who}: steps_per_chunk is None or an integer in [1, {_codec.MAX_STEPS}], got {R!r}")
+        targets = None if qualities is None else self._transcode_qualities(qualities, len(streams), who)
+        parsed = []
+        for m, d in enumerate(streams):
+            parsed.append(self._parse_image(d, *self._build_id()))
+            self._check_stream(parsed[-1][0], who, f"stream {m}")
+        return streams, parsed, targets
+
+    def _transcode_decode_z(self, parsed, idx):
+        """(the decoded integers of z, what h_s reads, its `_prior_each`) for the streams `idx`, which share a padded
+        size and a chunk size; `_begin_decode` has run for them."""
+        hs = [parsed[m][0] for m in idx]
+        k_z = self.entropy_model.decompress_seg([parsed[m][3] for m in idx], hs[0].z_shape, [parsed[m][1] for m in idx],
+                                                [h.kmax_z for h in hs], hs[0].R)
+        z_hat = self._hyper_ungain(k_z)
+        sigma, mean = self._prior_each(z_hat)
+        if tuple(sigma.shape[1:]) != hs[0].y_shape[1:]:
+            raise ValueError(f"transcode_each: the model's sigma {tuple(sigma.shape)} is not the streams' latent shape "
+                             f"{hs[0].y_shape}")
+        return k_z, z_hat, sigma, mean
+
+    def _transcode_decode_y(self, parsed, idx, rows):
+        """The decoded integers of y of the streams `idx`, flat floats in (n, *, c) order: the residual where the
+        model codes y about a mean, which is not added."""
+        hs = [parsed[m][0] for m in idx]
+        cm = self.conditional_model
+        return _decode_seg([parsed[m][4] for m in idx], [parsed[m][2] for m in idx], hs[0].nsym_y, rows, 0,
+                           lambda K: cm.tables(K, rows.device), [h.kmax_y for h in hs], hs[0].R, rows.device)
+
+    def _rechunk_group(self, parsed, idx, R):
+        """The streams `idx` (one padded size, one chunk size) coded again at R steps per chunk: their symbols, the
+        rows of their sigma computed once, and their headers with R replaced."""
+        em, cm = self.entropy_model, self.conditional_model
+        hs = [parsed[m][0] for m in idx]
+        self._begin_decode(hs)
+        k_z, _z_hat, sigma, _mean = self._transcode_decode_z(parsed, idx)
+        rows = cm.scale_rows(sigma)
+        k_y = self._transcode_decode_y(parsed, idx, rows)
+        sz = em.encode_symbols_seg(_to_last(k_z).reshape(-1).to(torch.int32), [h.kmax_z for h in hs], R)
+        sy = _encode_seg(k_y.to(torch.int32), len(idx), rows, 0, lambda K: cm.tables(K, rows.device),
+                         [h.kmax_y for h in hs], R)
+        return [self._pack_image(_codec.transcoded_header(h, R=int(R)), sz[k][1], sy[k][1], sz[k][0], sy[k][0])
+                for k, h in enumerate(hs)]
+
+    def _transcode_groups(self, parsed, todo):
+        """{(H, W, latent channels, R): [m]} of the streams `todo`, as `decompress_each` groups them."""
+        groups = {}
+        for m in todo:
+            h = parsed[m][0]
+            groups.setdefault((h.H, h.W, h.latent_channels, h.R), []).append(m)
+        return groups
+
+    @torch.no_grad()
+    def transcode_each(self, streams, qualities=None, steps_per_chunk=None):
+        """A list of M per-image streams of this model (any sizes, coded in any calls) -> a list of M streams, without
+        g_a, g_s or a pixel: the rules are codec.py's.  Eval mode only.
+
+        steps_per_chunk: None keeps every stream's own R; an int in [1, codec.MAX_STEPS] writes every output at that R.
+        qualities None is re-chunking only: the symbols of z and of y are decoded and coded again, the header is the
+        parsed one with R replaced, and the result is byte for byte what `compress_each` writes at that R.  A stream
+        that already has the target R is returned as the same object, with no launch for it.
+        qualities given (one float, or M of them) requantizes every stream to that quality: on
+        GainedMeanScaleCompressor2018 only (ValueError here).  `decompress_each` and `decompress_window` read the
+        results as they read any stream.  Everything is parsed, checked and planned before any launch; streams that
+        share a padded size and a chunk size go through the same launches."""
+        who = "transcode_each"
+        streams, parsed, targets = self._transcode_parse(streams, steps_per_chunk, who, qualities)
+        out = list(streams)
+        requant = [] if targets is None else [m for m, p in enumerate(parsed) if targets[m] != p[0].quality]
+        moved = set(requant)
+        rechunk = [m for m, p in enumerate(parsed)
+                   if steps_per_chunk is not None and p[0].R != steps_per_chunk and m not in moved]
+        try:
+            for idx in self._transcode_groups(parsed, rechunk).values():
+                for m, s in zip(idx, self._rechunk_group(parsed, idx, steps_per_chunk)):
+                    out[m] = s
+            for (_H, _W, _C, R), idx in self._transcode_groups(parsed, requant).items():
+                res = self._requant_group(parsed, idx, [targets[m] for m in idx], steps_per_chunk or R, who)
+                for m, s in zip(idx, res):
+                    out[m] = s
+        finally:
+            self._end_call()
         return out
 
     # ---- encode-time latent refinement: lower R + lambda D for this image, same decoder (codec.py states the rule)

@@ -60,6 +60,8 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
     window_refusal = ("CheckerboardCompressor2018 is not covered: y is coded as two gathered halves, anchors and "
                       "non-anchors, so a band of latent rows is not a range of chunks, and the non-anchors' (sigma, mu) "
                       "need the anchors around them")
+    transcode_refusal = ("CheckerboardCompressor2018 is not covered: its streams hold y as two bitstreams, anchors and "
+                         "non-anchors, and the non-anchors' (sigma, mu) depend on the anchors as decoded")
 
     def __init__(self, cfg):
         super().__init__(cfg)

@@ -208,8 +208,12 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
         who = "compress_each_to"
         if x.dim() != 4 or min(x.shape) < 1:
             raise ValueError(f"{who}: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
-        N = x.shape[0]
+        return self._check_budget_args(who, x.shape[0], "images", budgets, steps_per_chunk, candidates, rounds)
 
+    @staticmethod
+    def _check_budget_args(who, N, what, budgets, steps_per_chunk, candidates, rounds):
+        """The budgets of a call on N images or streams (`what`), one int each, and the checks of the search's
+        arguments."""
         def integer(v):
             return isinstance(v, (int, np.integer)) and not isinstance(v, bool)
 
@@ -220,7 +224,7 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
         else:
             raise ValueError(f"{who}: budgets are one positive int or a sequence of them, got {budgets!r}")
         if len(budgets) != N:
-            raise ValueError(f"{who}: {len(budgets)} budgets for {N} images")
+            raise ValueError(f"{who}: {len(budgets)} budgets for {N} {what}")
         if not all(integer(b) and b > 0 for b in budgets):
             raise ValueError(f"{who}: a budget is a positive int, a number of bytes, got {budgets!r}")
         for name, v, lo, hi in (("candidates", candidates, 2, 64), ("rounds", rounds, 1, 4),
@@ -228,8 +232,42 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
             if not integer(v) or not lo <= v <= hi:
                 raise ValueError(f"{who}: {name} is an integer in [{lo}, {hi}], got {v!r}")
         if N * candidates > 65535:
-            raise ValueError(f"{who}: {N} images x {candidates} candidates exceed the 65535 segments of one launch")
+            raise ValueError(f"{who}: {N} {what} x {candidates} candidates exceed the 65535 segments of one launch")
         return [int(b) for b in budgets]
+
+    def _budget_rounds(self, budgets, todo, measured, candidates, rounds, strict, measure):
+        """The round loop of codec.py's search rule, shared by `compress_each_to` and `transcode_each_to`.
+        budgets {n: bytes}; todo {n: the qualities of round 1}, consumed; measured {n: {quality: bytes}}, extended by
+        everything the rounds measure; measure([(n, q)]) -> ([bytes of candidate m], keep) measures one round's
+        candidates in one set of launches, keep(m) being what the final coding needs of candidate m.  Returns
+        ({n: the chosen quality}, {n: keep(its candidate)}); a miss in round 1 is a BudgetError (strict) or the
+        round's first quality."""
+        chosen, kept = {}, {}
+        for rnd in range(rounds):
+            cands = [(n, q) for n in sorted(todo) for q in todo[n]]
+            if not cands:
+                break
+            img, qs = [n for n, _ in cands], [q for _, q in cands]
+            size, keep = measure(cands)
+            for n in sorted(todo):
+                ms = [m for m in range(len(cands)) if img[m] == n]
+                measured[n].update((qs[m], size[m]) for m in ms)
+                pick = _codec.budget_choice([qs[m] for m in ms], [size[m] for m in ms], budgets[n])
+                if pick is None and rnd == 0:
+                    smallest = min(size[m] for m in ms)
+                    if strict:
+                        raise _codec.BudgetError(n, budgets[n], smallest)
+                    pick = qs[ms[0]]     # quality 0, the grid's first: the one stream that may exceed its budget
+                    del todo[n]
+                if pick is not None:
+                    chosen[n] = pick
+                    kept[n] = keep(ms[[qs[k] for k in ms].index(pick)])
+            for n in list(todo):
+                nxt = _codec.budget_next(measured[n], chosen[n])
+                todo[n] = [] if nxt is None else _codec.budget_refine(chosen[n], nxt, candidates)
+                if not todo[n]:
+                    del todo[n]     # chosen is S-1, or no float32 lies between it and the next one measured
+        return chosen, kept
 
     @torch.no_grad()
     def compress_each_to(self, x, budgets, steps_per_chunk=1024, candidates=8, rounds=2, strict=True):
@@ -269,54 +307,37 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
                 y_tables[K] = cm.tables(K, y.device)
             return y_tables[K]
 
-        measured = [{} for _ in range(N)]   # quality -> bytes, everything measured for the image so far
-        chosen = [None] * N                 # quality -> what the final coding needs of that candidate
-        kept = [None] * N
+        def measure(cands):
+            img, qs = [n for n, _ in cands], [q for _, q in cands]
+            M = len(cands)
+            self._use(qs)
+            g_y, _, g_z, g_inv_z = self._gains
+            try:
+                z_sym, kz = symbolize_seg(channel_scale(z[torch.as_tensor(img, device=z.device)], g_z))
+                z_hat = channel_scale(symbols_as_tensor(z_sym.to(torch.float32), (M, *z.shape[1:])), g_inv_z)
+                sigma, mean = self._prior_each(z_hat)
+                y_sym, ky = gain_symbolize_seg(y, g_y, mean, img)
+            except ValueError as e:
+                raise ValueError(f"{who}: among the candidates {cands}: {e}") from None
+            rows = cm.scale_rows(sigma.expand_as(mean))
+            lz = measure_seg(z_sym, M, None, em.channels, *table_pool(tables_z, kz), R)
+            ly = measure_seg(y_sym, M, rows, 0, *table_pool(tables_y, ky), R)
+            lens = torch.cat([lz, ly]).cpu().numpy().astype(np.int64)    # the one D2H copy of the round
+            lz, ly = lens[:lz.numel()].reshape(M, -1), lens[lz.numel():].reshape(M, -1)
+            fixed = _codec.gained_image_fixed_bytes(self._header(1, H, W, y, z, R, 0, 0, (h, w)))
+            size = [_codec.image_stream_bytes(fixed, lz[m], ly[m]) for m in range(M)]
+            nz, ny = z_sym.numel() // M, y_sym.numel() // M
+
+            def keep(m):
+                return (z_sym[m * nz:(m + 1) * nz].clone(), kz[m], y_sym[m * ny:(m + 1) * ny].clone(), ky[m],
+                        sigma[m:m + 1].clone(), mean[m:m + 1].clone(), size[m])
+            return size, keep
+
+        measured = {n: {} for n in range(N)}   # quality -> bytes, everything measured for the image so far
         todo = {n: _codec.budget_grid(self.levels, candidates) for n in range(N)}
         try:
-            for rnd in range(rounds):
-                cands = [(n, q) for n in sorted(todo) for q in todo[n]]
-                if not cands:
-                    break
-                img, qs = [n for n, _ in cands], [q for _, q in cands]
-                M = len(cands)
-                self._use(qs)
-                g_y, _, g_z, g_inv_z = self._gains
-                try:
-                    z_sym, kz = symbolize_seg(channel_scale(z[torch.as_tensor(img, device=z.device)], g_z))
-                    z_hat = channel_scale(symbols_as_tensor(z_sym.to(torch.float32), (M, *z.shape[1:])), g_inv_z)
-                    sigma, mean = self._prior_each(z_hat)
-                    y_sym, ky = gain_symbolize_seg(y, g_y, mean, img)
-                except ValueError as e:
-                    raise ValueError(f"{who}: among the candidates {cands}: {e}") from None
-                rows = cm.scale_rows(sigma.expand_as(mean))
-                lz = measure_seg(z_sym, M, None, em.channels, *table_pool(tables_z, kz), R)
-                ly = measure_seg(y_sym, M, rows, 0, *table_pool(tables_y, ky), R)
-                lens = torch.cat([lz, ly]).cpu().numpy().astype(np.int64)    # the one D2H copy of the round
-                lz, ly = lens[:lz.numel()].reshape(M, -1), lens[lz.numel():].reshape(M, -1)
-                fixed = _codec.gained_image_fixed_bytes(self._header(1, H, W, y, z, R, 0, 0, (h, w)))
-                size = [_codec.image_stream_bytes(fixed, lz[m], ly[m]) for m in range(M)]
-                nz, ny = z_sym.numel() // M, y_sym.numel() // M
-                for n in sorted(todo):
-                    ms = [m for m in range(M) if img[m] == n]
-                    measured[n].update((qs[m], size[m]) for m in ms)
-                    pick = _codec.budget_choice([qs[m] for m in ms], [size[m] for m in ms], budgets[n])
-                    if pick is None and rnd == 0:
-                        smallest = min(size[m] for m in ms)
-                        if strict:
-                            raise _codec.BudgetError(n, budgets[n], smallest)
-                        pick = qs[ms[0]]     # quality 0, the grid's first: the one stream that may exceed its budget
-                        del todo[n]
-                    if pick is not None:
-                        m = ms[[qs[k] for k in ms].index(pick)]
-                        chosen[n] = pick
-                        kept[n] = (z_sym[m * nz:(m + 1) * nz].clone(), kz[m], y_sym[m * ny:(m + 1) * ny].clone(), ky[m],
-                                   sigma[m:m + 1].clone(), mean[m:m + 1].clone(), size[m])
-                for n in list(todo):
-                    nxt = _codec.budget_next(measured[n], chosen[n])
-                    todo[n] = [] if nxt is None else _codec.budget_refine(chosen[n], nxt, candidates)
-                    if not todo[n]:
-                        del todo[n]     # chosen is S-1, or no float32 lies between it and the next one measured
+            chosen, kept = self._budget_rounds(dict(enumerate(budgets)), todo, measured, candidates, rounds, strict, measure)
+            chosen, kept = [chosen[n] for n in range(N)], [kept[n] for n in range(N)]
             self._use(chosen)
             z_sym, y_sym = (torch.cat([k[i] for k in kept]) for i in (0, 2))
             sigma, mean = (torch.cat([k[i] for k in kept]) for i in (4, 5))
@@ -332,3 +353,157 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
                 raise RuntimeError(f"{who}: the stream of image {n} at quality {chosen[n]} holds {len(s)} bytes, "
                                    f"{kept[n][6]} were measured")
         return streams, chosen
+
+    # ---- transcoding in the latent domain: a stream at quality q1 to quality q2, or to a byte budget, from its integers
+    # alone (codec.py states the requantization rule and the search's two differences)
+    def _transcode_qualities(self, qualities, M, who):
+        if isinstance(qualities, (str, bytes)):
+            raise ValueError(f"{who}: a quality is a number in [0, {self.levels - 1}], got {qualities!r}")
+        if isinstance(qualities, (list, tuple, np.ndarray, torch.Tensor)) and getattr(qualities, "ndim", 1) > 0:
+            qs = [_as_quality(v.item() if hasattr(v, "item") else v, self.levels) for v in qualities]
+            if len(qs) != M:
+                raise ValueError(f"{who}: {len(qs)} qualities for {M} streams")
+            return qs
+        return [_as_quality(qualities.item() if hasattr(qualities, "item") else qualities, self.levels)] * M
+
+    def _requant_decode(self, parsed, idx):
+        """What the requantizer reads of the streams `idx` (one padded size, one chunk size), decoded once however many
+        targets follow: (z_hat1, r1 (N, C, *), mu1, g_y'(q1) (N, C))."""
+        from ..blocks.entropy_model import symbols_as_tensor
+        hs = [parsed[m][0] for m in idx]
+        self._begin_decode(hs)
+        g_inv_y = self._gains[1]
+        _k_z, z_hat, sigma, mean = self._transcode_decode_z(parsed, idx)
+        r = self._transcode_decode_y(parsed, idx, self.conditional_model.scale_rows(sigma))
+        return z_hat, symbols_as_tensor(r, tuple(mean.shape)), mean, g_inv_y
+
+    def _requant_targets(self, decoded, img, qs):
+        """(symbols of z, kmax_z, symbols of y, kmax_y, sigma2, mu2) of the targets (source img[m], quality qs[m]) of
+        one `_requant_decode`, by the requantization rule: one set of launches for all of them."""
+        from ...functional import requant_seg
+        from ..blocks.entropy_model import symbolize_seg, symbols_as_tensor
+        z_hat1, r, mu1, g_inv_y1 = decoded
+        M = len(img)
+        self._use(qs)
+        g_y, _, g_z, g_inv_z = self._gains
+        src = z_hat1 if list(img) == list(range(z_hat1.shape[0])) else z_hat1[torch.as_tensor(img, device=z_hat1.device)]
+        z_sym, kz = symbolize_seg(channel_scale(src, g_z))
+        z_hat2 = channel_scale(symbols_as_tensor(z_sym.to(torch.float32), (M, *z_hat1.shape[1:])), g_inv_z)
+        sigma, mean = self._prior_each(z_hat2)
+        y_sym, ky = requant_seg(r, mu1, g_inv_y1, g_y, mean, img)
+        return z_sym, kz, y_sym, ky, sigma, mean
+
+    def _requant_group(self, parsed, idx, targets, R, who):
+        """The streams `idx` requantized to `targets`, one quality each, at R steps per chunk."""
+        from ..blocks.entropy_model import _encode_seg
+        em, cm = self.entropy_model, self.conditional_model
+        hs = [parsed[m][0] for m in idx]
+        decoded = self._requant_decode(parsed, idx)
+        try:
+            z_sym, kz, y_sym, ky, sigma, mean = self._requant_targets(decoded, range(len(idx)), targets)
+        except ValueError as e:
+            raise ValueError(f"{who}: among the streams {list(idx)} at the qualities {list(targets)}: {e}") from None
+        rows = cm.scale_rows(sigma.expand_as(mean))
+        sz = em.encode_symbols_seg(z_sym, kz, R)
+        sy = _encode_seg(y_sym, len(idx), rows, 0, lambda K: cm.tables(K, rows.device), ky, R)
+        return [self._pack_image(_codec.transcoded_header(h, R=int(R), quality=targets[k], kmax_z=kz[k], kmax_y=ky[k]),
+                                 sz[k][1], sy[k][1], sz[k][0], sy[k][0]) for k, h in enumerate(hs)]
+
+    @torch.no_grad()
+    def transcode_each_to(self, streams, budgets, steps_per_chunk=None, candidates=8, rounds=2, strict=True):
+        """`compress_each_to` for someone who holds only the streams: a list of M "ICRQ" streams of this model and
+        `budgets` (one positive int, or M of them: bytes of the whole stream, header included) -> (a list of M
+        streams, their float32 qualities), every stream with len(stream) <= budget, without g_a, g_s or a pixel.
+        `model.quality` is not looked at and not changed.
+
+        A stream is first re-chunked where `steps_per_chunk` asks for another R (no loss); one that then fits its
+        budget is the result at its own quality -- with no re-chunk asked the same object: no generation is lost
+        where none is needed.  Otherwise the search rule of codec.py runs on the sizes the coder reports for the
+        requantized candidates (`measure_seg`), round 1 being the grid below the stream's quality and the stream's
+        own size the upper end of every refinement.  The streams of a group are decoded once; all candidates of all
+        of them are requantized and measured by one set of launches per round, and only chunk lengths come back.
+
+        A stream that fits at no quality of round 1 (or is already at quality 0): codec.BudgetError (.image the
+        stream's index) in front of any packing of a requantized stream -- for a stream at quality 0 that already has
+        the target R in front of any launch; one that must be re-chunked is judged at its re-chunked length.  With
+        strict=False it is returned at quality 0 and is the one result
+        that may exceed its budget."""
+        from ...functional import measure_seg
+        from ..blocks.entropy_model import _encode_seg, table_pool
+        who = "transcode_each_to"
+        streams, parsed, _ = self._transcode_parse(streams, steps_per_chunk, who)
+        budgets = self._check_budget_args(who, len(streams), "streams", budgets,
+                                          1 if steps_per_chunk is None else steps_per_chunk, candidates, rounds)
+        em, cm = self.entropy_model, self.conditional_model
+        if strict:      # what the headers alone show, in front of any launch: quality 0, its final R, too large
+            for m, (h, *_rest) in enumerate(parsed):
+                if h.quality == 0.0 and h.R == (steps_per_chunk or h.R) and len(streams[m]) > budgets[m]:
+                    raise _codec.BudgetError(m, budgets[m], len(streams[m]))
+        if steps_per_chunk is not None and any(p[0].R != steps_per_chunk for p in parsed):
+            streams = self.transcode_each(streams, steps_per_chunk=steps_per_chunk)
+            parsed = [self._parse_image(d, *self._build_id()) for d in streams]
+        out, qualities = list(streams), [p[0].quality for p in parsed]
+        search = [m for m, d in enumerate(streams) if len(d) > budgets[m]]
+        grids = {m: _codec.transcode_grid(self.levels, candidates, parsed[m][0].quality) for m in search}
+        for m in search:
+            if not grids[m]:      # at quality 0, nothing below it, and too large even as re-chunked
+                if strict:
+                    raise _codec.BudgetError(m, budgets[m], len(streams[m]))
+        search = [m for m in search if grids[m]]
+        z_tables, y_tables = {}, {}     # one table per K and tensor kind for the whole call
+
+        def tables_z(K):
+            if K not in z_tables:
+                z_tables[K] = em.tables(K)
+            return z_tables[K]
+
+        def tables_y(K):
+            if K not in y_tables:
+                y_tables[K] = cm.tables(K, next(self.parameters()).device)
+            return y_tables[K]
+
+        found = []     # per group: (its streams, R, {m: chosen quality}, {m: what the final coding needs})
+        try:
+            for (_H, _W, _C, R), idx in self._transcode_groups(parsed, search).items():
+                local = {m: k for k, m in enumerate(idx)}
+                decoded = self._requant_decode(parsed, idx)
+                fixed = _codec.gained_image_fixed_bytes(parsed[idx[0]][0])
+
+                def measure(cands):
+                    img, qs = [local[m] for m, _ in cands], [q for _, q in cands]
+                    M = len(cands)
+                    try:
+                        z_sym, kz, y_sym, ky, sigma, mean = self._requant_targets(decoded, img, qs)
+                    except ValueError as e:
+                        raise ValueError(f"{who}: among the candidates (stream, quality) {cands}: {e}") from None
+                    rows = cm.scale_rows(sigma.expand_as(mean))
+                    lz = measure_seg(z_sym, M, None, em.channels, *table_pool(tables_z, kz), R)
+                    ly = measure_seg(y_sym, M, rows, 0, *table_pool(tables_y, ky), R)
+                    lens = torch.cat([lz, ly]).cpu().numpy().astype(np.int64)    # the one D2H copy of the round
+                    lz, ly = lens[:lz.numel()].reshape(M, -1), lens[lz.numel():].reshape(M, -1)
+                    size = [_codec.image_stream_bytes(fixed, lz[m], ly[m]) for m in range(M)]
+                    nz, ny = z_sym.numel() // M, y_sym.numel() // M
+
+                    def keep(m):
+                        return (z_sym[m * nz:(m + 1) * nz].clone(), kz[m], y_sym[m * ny:(m + 1) * ny].clone(), ky[m],
+                                rows[m * ny:(m + 1) * ny].clone(), size[m])
+                    return size, keep
+
+                measured = {m: _codec.transcode_measured(parsed[m][0].quality, len(streams[m])) for m in idx}
+                chosen, kept = self._budget_rounds({m: budgets[m] for m in idx}, {m: grids[m] for m in idx}, measured,
+                                                   candidates, rounds, strict, measure)
+                found.append((idx, R, chosen, kept))
+            for idx, R, chosen, kept in found:      # every stream has its quality: nothing was packed before this
+                z_sym, y_sym, rows = (torch.cat([kept[m][i] for m in idx]) for i in (0, 2, 4))
+                kz, ky = ([kept[m][i] for m in idx] for i in (1, 3))
+                sz = em.encode_symbols_seg(z_sym, kz, R)
+                sy = _encode_seg(y_sym, len(idx), rows, 0, tables_y, ky, R)
+                for k, m in enumerate(idx):
+                    h = _codec.transcoded_header(parsed[m][0], quality=chosen[m], kmax_z=kz[k], kmax_y=ky[k])
+                    out[m], qualities[m] = self._pack_image(h, sz[k][1], sy[k][1], sz[k][0], sy[k][0]), chosen[m]
+                    if len(out[m]) != kept[m][5]:
+                        raise RuntimeError(f"{who}: stream {m} at quality {chosen[m]} holds {len(out[m])} bytes, "
+                                           f"{kept[m][5]} were measured")
+        finally:
+            self._end_call()
+        return out, qualities

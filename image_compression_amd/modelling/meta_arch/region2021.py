@@ -198,6 +198,14 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
         raise ValueError("compress_each_to searches one quality per image: a byte budget for a quality map is not built; "
                          "use GainedMeanScaleCompressor2018 for budgets")
 
+    def _transcode_qualities(self, qualities, M, who):
+        raise ValueError(f"{who}: the streams of RegionGainedMeanScaleCompressor2018 carry a quality map: requantizing a "
+                         "map to another map is not built; leave `qualities` None to re-chunk")
+
+    def transcode_each_to(self, streams, budgets, steps_per_chunk=None, candidates=8, rounds=2, strict=True):
+        raise ValueError("transcode_each_to searches one quality per stream: a byte budget for a quality map is not "
+                         "built; use GainedMeanScaleCompressor2018 for budgets")
+
     def _analyse(self, x, each=False):
         N, _, H, W = x.shape
         self._use_map(self._call_map(N, H, W, "compress_each" if each else "compress", each), x.device)

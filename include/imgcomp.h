@@ -774,6 +774,24 @@ int ic_codec_decode_window(const void* in, size_t in_bytes, const ic_window* win
  * x[:, :, top : top + h, left : left + w] (any strides >= 0); one pass, bit for bit the two bounds then the slice */
 int ic_crop_clamp_at(const ic_act* x, int top, int left, int h, int w, float* y, void* stream);
 
+/* ---- transcoding in the latent domain (additive to version 4; Compressor2018.transcode_each,
+ *      GainedMeanScaleCompressor2018.transcode_each_to).  The symbols of y at other qualities from the decoded integers
+ *      of a stream, without y_hat or any scaled latent in memory.  IC_ERR_ARG before any launch for a null pointer, N
+ *      or nseg outside 1 .. 65535, P or C below 1, an extent beyond 2^63 or an img entry outside [0, N); no
+ *      floating-point atomics. ---- */
+/* r, mu1: the decoded float integers of y of N source streams and their means, dense (N, P, C) storage, channel
+ * fastest, read in place; a (N, C): the sources' inverse gains.  Target m of nseg names its source img[m] (host array,
+ * checked, then copied to img_dev: nseg ints on the device), its gain row b[m] of b (nseg, C) and its mean mu2[m] of
+ * mu2 (nseg, P, C):
+ *     sym[m][p][c] = the symbol of (((r[img[m]][p][c] + mu1[img[m]][p][c]) * a[img[m]][c]) * b[m][c]) - mu2[m][p][c]
+ * the sum ic_add_mean's one fp32 addition, each product ic_channel_scale's one fp32 multiplication, the difference and
+ * the symbol those of ic_codec_symbolize_mean_seg, none contracted: bit for bit those four calls on the gathered
+ * batch.  kmax_dev / kmax_host as in ic_gain_symbolize_seg: the maximum |symbol| of every target, one copy of the nseg
+ * maxima and one wait for the stream, IC_ERR_ARG (with kmax_host filled) when any exceeds IC_CODEC_KMAX. */
+int ic_requant_seg(const float* r, const float* mu1, long long N, long long P, int C, const float* a, const float* b,
+                   const float* mu2, int nseg, const int* img, int* img_dev, int* sym, int* kmax_dev, int* kmax_host,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -45,6 +45,12 @@ symbolize_mean_seg on one round's candidates, by device events.  --out profiles/
 images (ms per image, best of --reps wall times), the cost of one refinement step by device events ((T steps - 0
 steps) / T) and, beside it, one g_s forward with its input-gradient backward.  --out profiles/codec_refine_bench.json.
 
+--transcode Q2 [--rechunk R] [--transcode-budget BYTES] takes 8 x 3 x 512 x 768 "ICRQ" streams ("x32" weights, ladder
+tables) from quality S - 1 to Q2, (a) through pixels (decompress_each, set_quality, compress_each) and (b) by
+transcode_each, alternately in one process; with a budget, transcode_each_to beside the search rule run on (a)-style
+calls; requant_seg beside add_mean + channel_scale x 2 + symbolize_mean_seg on the same operands, by device events; and
+the PSNR and the sizes of both routes beside direct coding at Q2.  --out profiles/codec_transcode_bench.json.
+
 --context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
 --each works on it too (its loop arm is then the fused model's own compress / decompress).
 
@@ -228,11 +234,23 @@ def main():
                          "compress_each_to (--candidates, --rounds)")
     ap.add_argument("--refine", type=int, default=None, metavar="T",
                     help="compress_each beside compress_each_refined with T steps at 8 x 3 x 512 x 768; ms per step")
-    ap.add_argument("--candidates", type=int, default=8, help="candidate qualities per round of --budget")
-    ap.add_argument("--rounds", type=int, default=2, help="rounds of --budget")
+    ap.add_argument("--candidates", type=int, default=8,
+                    help="candidate qualities per round of --budget / --transcode-budget")
+    ap.add_argument("--rounds", type=int, default=2, help="rounds of --budget / --transcode-budget")
+    ap.add_argument("--transcode", type=float, default=None, metavar="Q2",
+                    help="8 x 3 x 512 x 768 streams at quality S - 1 taken to Q2: decompress_each + set_quality + "
+                         "compress_each against transcode_each; requant_seg beside the four ops it replaces")
+    ap.add_argument("--rechunk", type=int, default=0, metavar="R", help="steps per chunk of --transcode's outputs")
+    ap.add_argument("--transcode-budget", type=int, default=0, metavar="BYTES", dest="transcode_budget",
+                    help="with --transcode: transcode_each_to BYTES per stream against the search through pixels")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.transcode is not None:
+        _emit(transcode_bench(args), args.out)
+        return
+    if args.transcode_budget or args.rechunk:
+        ap.error("--transcode-budget and --rechunk go with --transcode Q2")
     if args.refine is not None:
         if args.refine < 0:
             ap.error("--refine: a number of steps >= 0")
@@ -995,6 +1013,169 @@ def refine_bench(args):
         model._clear_reparameterised()
     if T:
         out["step_over_g_s_pair"] = round(out["step_ms_by_events"] / out["g_s_forward_and_dgrad_ms_by_events"], 3)
+    return out
+
+
+def transcode_bench(args):
+    """--transcode Q2 [--rechunk R] [--transcode-budget BYTES]: 8 x 3 x 512 x 768 images coded at quality S - 1 and taken to
+    Q2 (a) through pixels -- decompress_each, set_quality, compress_each -- and (b) by transcode_each, alternately in
+    one process, device synchronised inside the timed region; with a budget, transcode_each_to beside the (a)-style
+    search (one decompress_each + compress_each per candidate of every round); requant_seg beside the four ops it
+    replaces on the same operands, by device events; and the PSNR and the sizes of both routes beside direct coding."""
+    from image_compression_amd import _lib, codec
+    from image_compression_amd import functional as F
+    N, H, W, reps, q2 = 8, 512, 768, args.reps, float(args.transcode)
+    Q, rounds, R1 = args.candidates, args.rounds, 1024
+    R2 = args.rechunk or None
+    scale = 32.0
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(N, 3, H, W, device="cuda", generator=g)
+    x *= torch.linspace(0.25, 1.0, N, device="cuda").view(N, 1, 1, 1)    # images that differ in their rate
+    out = {"metric": f"{N} x 3 x {H} x {W} streams from quality S - 1 to {q2}"
+                     f"{'' if R2 is None else f' and {R2} steps per chunk'}: decompress_each + set_quality + compress_each "
+                     f"against transcode_each, weight cache, best of {reps} alternating reps",
+           "unit": "ms per call", "reps": reps, "weight_scale": scale, "target_quality": q2, "rechunk": R2,
+           "data": "synthetic uniform [0,1) images scaled by 0.25 .. 1, resident in HBM; random-init weights (reference "
+                   "init, seed 0), ladder tables +-0.3 per level"}
+
+    def psnr(a, b):
+        return round(float(-10.0 * torch.log10(((a - b) ** 2).mean())), 3)
+
+    def timed(routes):
+        t = {k: [] for k in routes}
+        for _ in range(reps):
+            for k, fn in routes.items():
+                t[k].append(_wall(fn, 1))
+        for k, v in t.items():
+            out[f"{k}_ms"], out[f"{k}_all_ms"] = round(min(v), 3), [round(u, 3) for u in v]
+        return {k: min(v) for k, v in t.items()}
+
+    with torch.no_grad(), F.weight_cache():
+        model = _build("GainedMeanScaleCompressor2018", scale)[0]
+        for name, sign in (("log_y", 1.0), ("log_inv_y", -1.0), ("log_z", 1.0), ("log_inv_z", -1.0)):
+            getattr(model.gain, name).copy_(sign * 0.3 * torch.arange(model.levels, device="cuda").view(-1, 1))
+        S = model.levels
+        q1 = float(S - 1)
+        model.set_quality(q1)
+        src = model.compress_each(x, steps_per_chunk=R1)
+        out["source_quality"], out["source_bytes"] = q1, [len(s) for s in src]
+
+        def pixels(q=q2, streams=src):
+            x_hat = torch.cat(model.decompress_each(streams))
+            model.set_quality(q if isinstance(q, float) else list(q))
+            return model.compress_each(x_hat, steps_per_chunk=R2 or R1)
+
+        def latent():
+            return model.transcode_each(src, qualities=q2, steps_per_chunk=R2)
+
+        for _ in range(2):
+            a, b = pixels(), latent()
+        best = timed({"through_pixels": pixels, "transcode_each": latent})
+        out["transcode_each_over_through_pixels"] = round(best["transcode_each"] / best["through_pixels"], 4)
+        out["transcode_each_no_slower"] = bool(best["transcode_each"] <= best["through_pixels"])
+        model.set_quality(q2)
+        direct = model.compress_each(x, steps_per_chunk=R2 or R1)
+        out["bytes"] = {"through_pixels": [len(s) for s in a], "transcode_each": [len(s) for s in b],
+                        "direct_at_target": [len(s) for s in direct]}
+        out["psnr_db"] = {k: psnr(torch.cat(model.decompress_each(v)), x)
+                          for k, v in (("source", src), ("through_pixels", a), ("transcode_each", b),
+                                       ("direct_at_target", direct))}
+        out["psnr_note"] = "random-init weights: recorded, nothing is claimed about rate-distortion"
+
+        if args.transcode_budget:
+            budget = args.transcode_budget
+            calls = {"naive": 0}
+
+            def naive():
+                """The search rule from (a)-style calls: every candidate of every round is one decompress_each +
+                set_quality + compress_each of all streams, each at its own candidate."""
+                seen = [codec.transcode_measured(q1, len(s)) for s in src]
+                best_ = [(q1, s) if len(s) <= budget else None for s in src]
+                todo = {n: codec.transcode_grid(S, Q, q1) for n in range(N) if best_[n] is None}
+                for rnd in range(rounds):
+                    if not todo:
+                        break
+                    new = [{} for _ in range(N)]
+                    for k in range(max(len(v) for v in todo.values())):
+                        qs = [todo[n][k] if n in todo and k < len(todo[n]) else 0.0 for n in range(N)]
+                        streams = pixels(qs)
+                        calls["naive"] += 1
+                        for n in todo:
+                            if k < len(todo[n]):
+                                new[n][qs[n]] = streams[n]
+                    for n in list(todo):
+                        seen[n].update((q, len(s)) for q, s in new[n].items())
+                        qs = sorted(new[n])
+                        pick = codec.budget_choice(qs, [len(new[n][q]) for q in qs], budget)
+                        if pick is None and rnd == 0:
+                            best_[n] = (qs[0], new[n][qs[0]])
+                            del todo[n]
+                            continue
+                        if pick is not None:
+                            best_[n] = (pick, new[n][pick])
+                        nxt = codec.budget_next(seen[n], best_[n][0])
+                        todo[n] = [] if nxt is None else codec.budget_refine(best_[n][0], nxt, Q)
+                        if not todo[n]:
+                            del todo[n]
+                return [v[1] for v in best_], [v[0] for v in best_]
+
+            def searched():
+                return model.transcode_each_to(src, budget, steps_per_chunk=R2, candidates=Q, rounds=rounds, strict=False)
+
+            for _ in range(2):
+                na, se = naive(), searched()
+            calls["naive"] = 0
+            na, se = naive(), searched()
+            rounds_through_pixels = calls["naive"]
+            best = timed({"naive_search_through_pixels": naive, "transcode_each_to": searched})
+            out["budget"] = {"bytes": budget, "candidates": Q, "rounds": rounds, "naive_rounds_through_pixels": rounds_through_pixels,
+                             "qualities": {"naive": na[1], "transcode_each_to": se[1]},
+                             "stream_bytes": {"naive": [len(s) for s in na[0]], "transcode_each_to": [len(s) for s in se[0]]},
+                             "within_budget": [len(s) <= budget for s in se[0]],
+                             "psnr_db": {"naive": psnr(torch.cat(model.decompress_each(na[0])), x),
+                                         "transcode_each_to": psnr(torch.cat(model.decompress_each(se[0])), x)}}
+            out["transcode_each_to_over_naive"] = round(best["transcode_each_to"] / best["naive_search_through_pixels"], 4)
+            out["transcode_each_to_no_slower"] = bool(best["transcode_each_to"] <= best["naive_search_through_pixels"])
+
+        # the kernel by device events, on the operands of the two calls: every stream to one target (transcode_each),
+        # and every stream to every quality of the grid below q1 (one round of transcode_each_to)
+        model._codable_each()
+        parsed = [model._parse_image(s, int(_lib.load().ic_version()), "fp32_split") for s in src]
+        z_hat1, r, mu1, a_inv = model._requant_decode(parsed, list(range(N)))
+        rl, m1l = F._to_last(r), F._to_last(mu1)
+        out["kernels_ms"], out["kernels_all_ms"] = {}, {}
+        for tag, cands in (("each", [(n, q2) for n in range(N)]),
+                           ("search", [(n, q) for n in range(N) for q in codec.transcode_grid(S, Q, q1)])):
+            img, qs = [n for n, _ in cands], [q for _, q in cands]
+            M = len(cands)
+            _, _, _, _, _, mu2 = model._requant_targets((z_hat1, r, mu1, a_inv), img, qs)
+            g_y = model.gain(qs)[0]
+            m2l = F._to_last(mu2)
+            idx = torch.as_tensor(img, device="cuda")
+            gather = img != list(range(N))
+
+            def four_ops():
+                rr, mm, aa = (rl[idx], m1l[idx], a_inv[idx]) if gather else (rl, m1l, a_inv)
+                y_hat = _lib.mean_ops().add_mean(rr.reshape(-1), mm).view(mm.shape)
+                scaled = _lib.gain_ops().channel_scale(_lib.gain_ops().channel_scale(y_hat, aa), g_y)
+                return _lib.mean_ops().symbolize_seg(scaled, m2l, M)
+
+            kern = {"requant_seg": lambda: F.requant_seg(r, mu1, a_inv, g_y, mu2, img),
+                    ("gather_" if gather else "") + "add_mean_channel_scale_x2_symbolize_mean_seg": four_ops}
+            same = bool(torch.equal(kern["requant_seg"]()[0], four_ops()[0]))
+            tk = {k: [] for k in kern}
+            for _ in range(reps):
+                for k, fn in kern.items():
+                    tk[k].append(_events(fn, 1))
+            out["kernels_ms"][tag] = {k: round(min(v), 4) for k, v in tk.items()}
+            out["kernels_all_ms"][tag] = {k: [round(u, 4) for u in v] for k, v in tk.items()}
+            out["kernels_ms"][tag].update(targets=M, symbols_per_target=int(mu2[0].numel()), same_symbols=same)
+            times = [min(v) for v in tk.values()]
+            out["kernels_ms"][tag]["requant_seg_no_slower"] = bool(times[0] <= times[1])
+        model._end_call()
+        out["kernels_note"] = ("device events around one call; both symbolizers include their copy of the maxima and their "
+                               "stream wait; cache rates, comparable with one another only")
+        out["requant_share_of_transcode_each"] = round(out["kernels_ms"]["each"]["requant_seg"] / out["transcode_each_ms"], 4)
     return out
 
 
