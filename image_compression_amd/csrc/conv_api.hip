@@ -47,7 +47,9 @@ int direct_im2col(const ic_act* x, const float* W, const float* bias, int k, int
                   const ic_act* y, int epi, void* ws, size_t wsb, hipStream_t s, size_t* need, int math = 0) {
   const int T = k * k;
   const int Kp = (int)ic_align((size_t)T * x->c, 32);
-  if ((epi == EPI_NONE || epi == EPI_RELU) && edge_conv_ok(x->c, k, stride, x->sw, y->sc, y->c, y->sw, y->sh, y->sn)) {
+  // edge_conv_ok holds y's strides to whole channel quads; edge_conv_run refuses a base off a 16-byte boundary
+  if ((epi == EPI_NONE || epi == EPI_RELU) && ((uintptr_t)y->data & 15) == 0 &&
+      edge_conv_ok(x->c, k, stride, x->sw, y->sc, y->c, y->sw, y->sh, y->sn)) {
     // patch-gather kernel (edge.hip): no im2col columns in HBM
     const int Npad = ig_npad(y->c);
     const size_t wpb = (size_t)Npad * Kp * 4;
@@ -125,7 +127,7 @@ int transposed_col2im(const ic_act* x, const float* W, const float* bias, int k,
   set_x(d, x);
   set_y(d, &yc);
   d.stride = 1;
-  d.generic = (x->c % 32 != 0) || (x->sc != 1);
+  d.generic = (x->c % 32 != 0) || (x->sc != 1) || !ig_x_vec16(x);
   d.bias = nullptr; d.epi = EPI_NONE; d.a_op = AOP_NONE;
   d.nphase = 1;
   IgPhase& P = d.ph[0];
@@ -175,13 +177,14 @@ int direct_impl(const ic_act* x, const float* W, const float* bias, int k, int s
   if (!act_fits32(x) || !act_fits32(y)) return IC_ERR_ARG;  // 32-bit element offsets in the kernels
   if ((x->h + 2 * pad - k) / stride + 1 != y->h || (x->w + 2 * pad - k) / stride + 1 != y->w)
     return IC_ERR_ARG;
-  if (x->c <= FEW_CH && aop == AOP_NONE)
+  // (5 x 5 taps of more than 5 channels make rows wider than im2col_run's: the gather form below)
+  if (x->c <= FEW_CH && aop == AOP_NONE && ic_align((size_t)k * k * x->c, 32) <= IM2COL_MAXKP)
     return direct_im2col(x, W, bias, k, stride, pad, y, epi, ws, wsb, s, need, math);
   IgDesc d = {};
   set_x(d, x);
   set_y(d, y);
   d.stride = stride;
-  d.generic = (x->c % 32 != 0) || (x->sc != 1);
+  d.generic = (x->c % 32 != 0) || (x->sc != 1) || !ig_x_vec16(x);
   d.bias = bias; d.epi = epi; d.a_op = aop;
   d.aux0 = aux0; d.aux1 = aux1; d.aux2 = aux2; d.aux_out = aux_out;
   d.nphase = 1;
@@ -252,7 +255,8 @@ int transposed_impl(const ic_act* x, const float* W, const float* bias, int k, i
   if (!act_fits32(x) || !act_fits32(y)) return IC_ERR_ARG;  // 32-bit element offsets in the kernels
   if ((y->h + 2 * pad - k) / stride + 1 != x->h || (y->w + 2 * pad - k) / stride + 1 != x->w)
     return IC_ERR_ARG;
-  if ((epi == EPI_NONE || epi == EPI_RELU) &&
+  // tconv_few_ok holds x compact with Cin % 16 == 0; tconv_few_run refuses a base off a 16-byte boundary
+  if ((epi == EPI_NONE || epi == EPI_RELU) && ((uintptr_t)x->data & 15) == 0 &&
       tconv_few_ok(x->c, y->c, k, stride, pad, x->sc, x->sw, x->sh, x->sn, x->h, x->w)) {
     // output-row-stationary kernel (edge.hip): no column buffer in HBM
     const int split = (EDGE_BF16 && (math & IC_MATH_BF16)) ? 2 : (math & IC_MATH_SPLIT) ? 1 : 0;
@@ -267,13 +271,13 @@ int transposed_impl(const ic_act* x, const float* W, const float* bias, int k, i
     return tconv_few_run(x->data, x->n, x->h, x->w, x->c, W, y->c, k, pad, bias, epi == EPI_RELU, y->data, y->sn,
                          y->sc, y->sh, y->sw, y->h, y->w, s, split);
   }
-  if (y->c <= FEW_CH && x->c % 32 == 0 && x->sc == 1)
+  if (y->c <= FEW_CH && x->c % 32 == 0 && x->sc == 1 && ig_x_vec16(x))
     return transposed_col2im(x, W, bias, k, stride, pad, y, epi, ws, wsb, s, need);
   IgDesc d = {};
   set_x(d, x);
   set_y(d, y);
   d.stride = 1;
-  d.generic = (x->c % 32 != 0) || (x->sc != 1);
+  d.generic = (x->c % 32 != 0) || (x->sc != 1) || !ig_x_vec16(x);
   d.bias = bias; d.epi = epi; d.a_op = AOP_NONE;
   int pky[IC_MAXPH][IC_MAXT], pkx[IC_MAXPH][IC_MAXT];
   int np = 0, tmax = 0;
@@ -441,8 +445,8 @@ int wgrad_impl(const ic_act* G, const ic_act* X, int k, int stride, int pad, flo
     return rc;
   }
   // few X channels: wgrad against xcol = im2col(X) on G's grid (1 tap, K = Kp)
-  const bool few = X->c <= FEW_CH;
   const int Kp = (int)ic_align((size_t)d.T * X->c, 32);
+  const bool few = X->c <= FEW_CH && Kp <= IM2COL_MAXKP;  // wider rows than im2col_run's: the GEMM on X itself
   size_t xcb = 0;
   if (few) {
     xcb = (size_t)G->n * G->h * G->w * Kp * 4;

@@ -48,7 +48,7 @@ void gemm1x1(IgDesc& d, const ic_act* x, const ic_act* y) {
   d.x = x->data; d.xs_n = x->sn; d.xs_h = x->sh; d.xs_w = x->sw; d.xs_c = x->sc;
   d.Hx = x->h; d.Wx = x->w; d.Cin = x->c; d.N = x->n; d.stride = 1;
   d.y = y->data; d.ys_n = y->sn; d.ys_h = y->sh; d.ys_w = y->sw; d.ys_c = y->sc; d.Cout = y->c;
-  d.generic = (x->c % 32 != 0) || (x->sc != 1);
+  d.generic = (x->c % 32 != 0) || (x->sc != 1) || !ig_x_vec16(x);
   d.nphase = 1;
   IgPhase& P = d.ph[0];
   P.T = 1; P.dy[0] = 0; P.dx[0] = 0;

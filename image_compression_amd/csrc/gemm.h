@@ -21,7 +21,7 @@ enum IgEpilogue {
   EPI_GDN_BWD = 4,    // y = aux2 / sqrt(aux1) + 2*aux0*v
   EPI_IGDN_BWD = 5    // y = aux2 * sqrt(aux1) + 2*aux0*v
 };
-enum IgAOp { AOP_NONE = 0, AOP_SQUARE = 1, AOP_ABS = 2 };
+enum IgAOp { AOP_NONE = 0, AOP_SQUARE = 1 };
 
 struct IgPhase {
   const float* wp;  // fast: [T][Npad][Cin]; generic: [Npad][Kpad]
@@ -130,6 +130,12 @@ static inline bool act_fits32(const ic_act* a) {
   }
   return mx < (1LL << 31) && (long long)a->n * a->h * a->w < (1LL << 31);
 }
+// The fast forms of the ig_* kernels read x 16 bytes at a time (float4 loads, LDS-DMA): its base and its three
+// pixel strides must keep that alignment, as wg_plan asks of its operands.  Any other x takes the gather form,
+// which loads element by element.  A null base (a workspace query without the tensor) counts as aligned.
+static inline bool ig_x_vec16(const ic_act* x) {
+  return ((uintptr_t)x->data & 15) == 0 && x->sw % 4 == 0 && x->sh % 4 == 0 && x->sn % 4 == 0;
+}
 // out[g][c][kk(t)] (+)= sum over splits; kk_of_t maps tap -> ky*k+kx, kk = k*k
 int wg_reduce(const WgDesc& d, float* out, const int* kk_of_t, int kk, hipStream_t s);
 
@@ -150,6 +156,7 @@ int pack_weights(const float* W, int A, int B, int k, int mode, int generic,
 // w = w0 + w1 + w2, plane stride = the pack's element count)
 
 // few-channel edges (im2col.hip)
+constexpr int IM2COL_MAXKP = 128;  // padded (tap, channel) columns im2col_run handles: wider rows take the gather form
 int im2col_run(const float* x, long long sn, long long sc, long long sh, long long sw, int N, int C, int H,
                int W, int Hg, int Wg, int stride, int k, int pad, int Kp, float* out, hipStream_t s);
 int col2im_run(const float* ycol, int ncol, int N, int Hi, int Wi, const float* bias, float* y, long long sn,

@@ -1320,8 +1320,10 @@ long long ig_grid_blocks(const IgDesc& d) {
 int ig_run(IgDesc& d, hipStream_t s) {
   if (d.Mtot == 0) return IC_OK;
   if (!d.generic && (d.Cin % 32 != 0 || d.xs_c != 1)) return IC_ERR_ARG;
+  // 16-byte loads of x (ig_x_vec16): the callers plan the gather form for any other x
+  if (!d.generic && (((uintptr_t)d.x & 15) || d.xs_w % 4 || d.xs_h % 4 || d.xs_n % 4)) return IC_ERR_ARG;
   if (d.bf16 && (d.generic || (ig_bf16_wide(d) && d.Cin % 64 != 0))) return IC_ERR_ARG;
-  if (d.x3 && (d.generic || d.bf16 || d.Cin % 32 != 0 || d.a_op == AOP_ABS || d.bn % 64 != 0)) return IC_ERR_ARG;
+  if (d.x3 && (d.generic || d.bf16 || d.Cin % 32 != 0 || d.bn % 64 != 0)) return IC_ERR_ARG;
   if (d.generic && (d.Kc % 32 != 0)) return IC_ERR_ARG;
   int rc;
   if (d.dma) {

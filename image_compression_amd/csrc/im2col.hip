@@ -9,7 +9,7 @@
 
 namespace {
 
-constexpr int MAXKP = 128;  // padded (tap, channel) columns handled by im2col
+constexpr int MAXKP = IM2COL_MAXKP;  // padded (tap, channel) columns handled by im2col
 
 struct Im2colArgs {
   const float* x;

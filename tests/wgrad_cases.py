@@ -105,6 +105,8 @@ CASES = [
     _tconv("t_edge_one_chunk", 2, 64, 16, 16, 3, 5, 2, 2, 1, kern=EDGE, bn=None, ns=(0, 0), views=("dy",)),  # 2 x 3 x 32 x 32
     _tconv("t_col_cin96", 2, 96, 20, 24, 3, 5, 2, 2, 1, kern=NARROW, bn=64, im2col=1, ns=(15, 15)),
     _tconv("t_col_cin80", 1, 80, 9, 7, 3, 5, 2, 2, 1, kern=NARROW, bn=64, im2col=1, ns=(1, 1)),       # db: 18 x 14 planes
+    # 25 taps x 6 channels = 150 columns, wider than the column buffer's 128: the gather form on dy itself
+    _tconv("t_gather_kp160", 1, 64, 9, 7, 6, 5, 2, 2, 1, kern=(GA,) * 4, bn=64, ns=(1, 1), dyfmt="nchw"),
 ]
 BY_NAME = {c.name: c for c in CASES}
 assert len(BY_NAME) == len(CASES)
