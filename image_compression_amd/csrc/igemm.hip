@@ -754,7 +754,12 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM == 64 ? 3 : 2)
 // stage that chunk c + 1's DMA, issued right after it, overwrites.  Each wave splits its own A
 // fragments into three bf16 terms after reading them (8 fp32 per lane per 16-row tile) — the 32
 // rows it DMAs, each split by one wave (64 x 96 wave tiles split every row in two waves: 2.6 %
-// slower on the big layers, 1.4 % per C2 step, r03zw) — and runs
+// slower on the big layers, 1.4 % per C2 step, r03zw).  Because the rows are the wave's own, it
+// splits chunk c + 1's late in chunk c's MFMA stream (IG_X3D_PRESPLIT, before n-tile
+// IG_X3D_PRESPLIT_J) into a second fragment set: s_waitcnt vmcnt(4) covers its four A pieces,
+// which issue() emits before its at most five B pieces — the wait depends on that order — and
+// the wave's own counter is all that orders its LDS reads behind its own DMA; only the B planes
+// need the barrier, after which the MFMAs start from registers.  It runs
 // ig_kernel_x3s's six products per (i, j) in the same order over the same chunk order, so the
 // result is bitwise that kernel's.  Per chunk a 256-row tile stages the weights once for twice
 // the rows of ig_kernel_x3s<128, ...> (68 vs 104 KB per 256 rows), and no VALU or ds_write
@@ -773,6 +778,18 @@ __global__ void __launch_bounds__(64 * (BM / WM) * (BN / WN), (BM == 64 ? 3 : 2)
 #ifndef IG_X3D_DMA_J
 #define IG_X3D_DMA_J 4  // DMA_AT 2: before n-tile j's MFMAs (r03zx-r03zy: j = 4 of 12, 1.7-2.7 % per C2 step over 0)
 #endif
+#ifndef IG_X3D_PRESPLIT
+#define IG_X3D_PRESPLIT 1  // chunk c + 1's A split: 0 after c + 1's barrier, 1 during chunk c before n-tile PRESPLIT_J, 2 spread from there
+#endif
+#ifndef IG_X3D_PRESPLIT_J
+#define IG_X3D_PRESPLIT_J 9  // PRESPLIT 1 / 2: before n-tile j's MFMAs, after the DMA issue (j > IG_X3D_DMA_J)
+#endif
+#ifndef IG_X3D_PRESPLIT_SGB
+#define IG_X3D_PRESPLIT_SGB 4  // PRESPLIT 2: VALU per MFMA (sched_group_barrier)
+#endif
+static_assert(!IG_X3D_PRESPLIT || (IG_X3D_WM == 32 && IG_X3D_DMA_AT == 2 && IG_X3D_PRESPLIT_J > IG_X3D_DMA_J &&
+                                   IG_X3D_PRESPLIT_J < 12),
+              "the pre-split reads the rows the wave itself DMAs (32-row wave tiles), after this chunk's DMA issue");
 #ifndef IG_X3D_MINT
 #define IG_X3D_MINT 32  // smaller grids: 256-row tiles with K split to fill the chip (>= this many tiles)
 #endif
@@ -857,6 +874,7 @@ __global__ void __launch_bounds__(512, 1) ig_kernel_x3d(const IgDesc d) {
     const uint32_t sb = lbase + (uint32_t)(st * STAGE);
     const int dy = P.dy[t], dx = P.dx[t];
     const uint32_t toff = (uint32_t)(dy * (int)xsh + dx * (int)xsw + cc * 32);
+    // the four A pieces first, then the B pieces: the pre-split's vmcnt(4) counts on this order
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int iy = a_iy[k] + dy, ix = a_ix[k] + dx;
@@ -886,16 +904,9 @@ __global__ void __launch_bounds__(512, 1) ig_kernel_x3d(const IgDesc d) {
 #pragma unroll
     for (int j = 0; j < TN; ++j) acc[i][j] = floatx4v{0.f, 0.f, 0.f, 0.f};
 
-  for (int c = cb; c < ce; ++c) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    const float* As = (const float*)(lds + ((c - cb) & 1) * STAGE);
-    const __bf16* Bs = (const __bf16*)(lds + ((c - cb) & 1) * STAGE + ASTAGE);
-    if (IG_X3D_DMA_AT == 1 && c + 1 < ce) {
-      issue(cn, tn, (c + 1 - cb) & 1);
-      if (++tn == T) { tn = 0; ++cn; }
-    }
-    bf16x8 a[3][TM];
+  // the wave's 32 A rows of stage st, read and split into the three bf16 terms (MFMA A fragments)
+  auto split_a = [&](int st, bf16x8 (&a)[3][TM]) {
+    const float* As = (const float*)(lds + st * STAGE);
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
       const float* ar = As + (wm * WM + i * 16 + r) * 32;
@@ -908,17 +919,26 @@ __global__ void __launch_bounds__(512, 1) ig_kernel_x3d(const IgDesc d) {
       a[1][i] = __builtin_shufflevector(m0v, m1v, 0, 1, 2, 3, 4, 5, 6, 7);
       a[2][i] = __builtin_shufflevector(l0, l1, 0, 1, 2, 3, 4, 5, 6, 7);
     }
-    // the next chunk's DMA, between the split (VALU) and the MFMAs (r03p: 1 % faster than before the split)
-    if (IG_X3D_DMA_AT == 0 && c + 1 < ce) {
-      issue(cn, tn, (c + 1 - cb) & 1);
+  };
+  // One chunk: st is its stage, a its split A fragments -- split here (IG_X3D_PRESPLIT 0), or already split
+  // during the chunk before; an receives the next chunk's.
+  auto chunk = [&](auto last, int c, int st, bf16x8 (&a)[3][TM], bf16x8 (&an)[3][TM]) {
+    constexpr bool LAST = decltype(last)::value;  // pre-split form: the range's last chunk, peeled
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    const __bf16* Bs = (const __bf16*)(lds + st * STAGE + ASTAGE);
+    if (IG_X3D_DMA_AT == 1 && c + 1 < ce) {
+      issue(cn, tn, st ^ 1);
       if (++tn == T) { tn = 0; ++cn; }
     }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      if (IG_X3D_DMA_AT == 2 && j == IG_X3D_DMA_J && c + 1 < ce) {
-        issue(cn, tn, (c + 1 - cb) & 1);
-        if (++tn == T) { tn = 0; ++cn; }
-      }
+    if (!IG_X3D_PRESPLIT) split_a(st, a);
+    // the next chunk's DMA, between the split (VALU) and the MFMAs (r03p: 1 % faster than before the split)
+    if (IG_X3D_DMA_AT == 0 && c + 1 < ce) {
+      issue(cn, tn, st ^ 1);
+      if (++tn == T) { tn = 0; ++cn; }
+    }
+    // n-tile j: its three B fragments and the six products of each row tile
+    auto tile = [&](int j) {
       bf16x8 b[3];
 #pragma unroll
       for (int q = 0; q < 3; ++q) b[q] = *(const bf16x8*)(Bs + (q * BN + wn * WN + j * 16 + r) * LDB + bch);
@@ -931,6 +951,67 @@ __global__ void __launch_bounds__(512, 1) ig_kernel_x3d(const IgDesc d) {
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[1], acc[i][j], 0, 0, 0);
         acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a[0][i], b[0], acc[i][j], 0, 0, 0);
       }
+    };
+    if constexpr (!IG_X3D_PRESPLIT) {
+#pragma unroll
+      for (int j = 0; j < TN; ++j) {
+        if (IG_X3D_DMA_AT == 2 && j == IG_X3D_DMA_J && c + 1 < ce) {
+          issue(cn, tn, st ^ 1);
+          if (++tn == T) { tn = 0; ++cn; }
+        }
+        tile(j);
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < IG_X3D_DMA_J; ++j) tile(j);
+      if constexpr (!LAST) {
+        issue(cn, tn, st ^ 1);
+        if (++tn == T) { tn = 0; ++cn; }
+      }
+#pragma unroll
+      for (int j = IG_X3D_DMA_J; j < IG_X3D_PRESPLIT_J; ++j) tile(j);
+      if constexpr (!LAST) {
+        // The wave's own four A pieces of chunk c + 1 have landed: issue() emits them before its B pieces, a
+        // wave has at most five of those, and loads retire in issue order.  The rows are the wave's own, so
+        // its counter alone orders these reads behind its DMA; the B planes wait for the barrier.
+        __builtin_amdgcn_sched_barrier(0);  // the earlier n-tiles' MFMAs stay ahead of the wait
+        asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        split_a(st ^ 1, an);
+      }
+#pragma unroll
+      for (int j = IG_X3D_PRESPLIT_J; j < TN; ++j) tile(j);
+      if constexpr (!LAST && IG_X3D_PRESPLIT == 2) {
+        // the split's VALU in the shadow of these n-tiles' MFMAs, IG_X3D_PRESPLIT_SGB per MFMA
+#pragma unroll
+        for (int k = 0; k < (TN - IG_X3D_PRESPLIT_J) * 6 * TM; ++k) {
+          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);                    // MFMA
+          __builtin_amdgcn_sched_group_barrier(0x002, IG_X3D_PRESPLIT_SGB, 0);  // VALU
+        }
+      }
+    }
+  };
+
+  bf16x8 a0[3][TM];
+  if constexpr (!IG_X3D_PRESPLIT) {
+    for (int c = cb; c < ce; ++c) chunk(std::false_type{}, c, (c - cb) & 1, a0, a0);
+  } else if (cb < ce) {
+    // The first chunk is split here, every later one during the chunk before it.  Two chunks per trip: the
+    // two fragment sets trade places without register copies (one chunk per trip and 24 copies: no faster
+    // than the in-loop split), and the stage is a constant.  The range's last chunk, which has nothing to
+    // issue or split, is peeled off, so each body is one straight line.
+    bf16x8 a1[3][TM];
+    asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+    split_a(0, a0);
+    int c = cb;
+    for (; c + 2 < ce; c += 2) {
+      chunk(std::false_type{}, c, 0, a0, a1);
+      chunk(std::false_type{}, c + 1, 1, a1, a0);
+    }
+    if (c + 2 == ce) {
+      chunk(std::false_type{}, c, 0, a0, a1);
+      chunk(std::true_type{}, c + 1, 1, a1, a0);
+    } else {
+      chunk(std::true_type{}, c, 0, a0, a1);
     }
   }
   ig_epilogue16<TM, TN>(d, P, acc, M, m0, 0, wm, wn, WM, WN, lane, split);
