@@ -270,6 +270,12 @@ SIGNATURES = {
     # ic_version 4)
     "ic_requant_seg": (c_int, [c_void, c_void, c_ll, c_ll, c_int, c_void, c_void, c_void, c_int, P(c_int), c_void,
                                c_void, c_void, P(c_int), c_void]),
+    # choosing a quality map under a byte budget: the per-block level choice, y's symbols under a level map (additive
+    # to ic_version 4)
+    "ic_block_allocate": (c_int, [c_void, c_void, c_int, c_int, c_ll, c_int, P(c_int), P(c_float), c_void, c_void,
+                                  c_void, c_void, c_void, c_void]),
+    "ic_block_gain_symbolize_seg": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_int, c_void,
+                                            c_int, P(c_int), c_void, c_void, c_void, P(c_int), c_void]),
 }
 
 _lib = None
@@ -298,6 +304,7 @@ rate_ops = _namespace("imgcomp_rate", "the sizes and the symbols of candidate st
 refine_ops = _namespace("imgcomp_refine", "the bookkeeping of encode-time latent refinement")
 window_ops = _namespace("imgcomp_window", "the decoder of a latent window and the crop at an offset")
 transcode_ops = _namespace("imgcomp_transcode", "y's symbols at other qualities from a stream's decoded integers")
+alloc_ops = _namespace("imgcomp_alloc", "the per-block level choice and y's symbols under a level map")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 
 

@@ -173,6 +173,30 @@ Sizes are not assumed monotone in the quality (the gain tables are learnt), so t
         `BudgetError` (strict), or the image is coded at quality 0 and is the one stream that may exceed its budget.
 The result is optimal relative to the qualities measured, not to the interval.
 
+A quality map under a byte budget (`RegionGainedMeanScaleCompressor2018.compress_each_map_to`): the allocation rule
+--------------------------------------------------------------------------------------------------------------------
+A budget B is a bound on len() of one image's "ICRR" stream, header and map included.  The map is chosen block by
+block at one slope t in [0, S-1] per image, and t is searched by the rule above; the budget is enforced on sizes the
+coder itself reports, so it is exact, while the tables that steer the choice are an estimate.
+    Levels.  The S integer levels q_l = l, l = 0 .. S-1; the code of level l is `map_level_codes(S)[l]` =
+        quality_code(l, S) and its gains are those of code_quality(code_l, S), as the uniform map of set_quality(l).
+    Tables.  bits[n, l, b] and sse[n, l, b], float32, (N, S, Hb Wb): bit for bit the `bits` and `sse` that
+        `rate_distortion_map(x)` returns on the same batch after set_quality(l).  g_a and h_a do not depend on the
+        quality and run once for the S levels.
+    Allocation at slope t (`map_allocate`).  w = `map_weight(loss_weight(t), x.shape[1])` = float32(lambda(t) / C), the
+        weight of `compress_each_refined`'s J = B + w D.  For every block b, J[l] = fadd(bits[l, b], fmul(w, sse[l, b])),
+        each operation rounded once in float32, none contracted.  l is scanned 0 .. S-1 ascending from best = 0 and
+        replaces best iff J[l] < J[best] (strict): a tie goes to the lower level, a NaN never wins.  The map holds
+        code_best(b).  It is the exact minimiser of the tabulated sum of J over independent per-block choices and
+        nothing more: neighbouring blocks share receptive fields, so the table is a steering estimate.
+    Search over t.  The search rule above, unchanged: round 1 is `budget_grid(S, Q)`, later rounds `budget_refine`,
+        with `budget_choice` and `budget_next`; sizes are not assumed monotone in t.  A miss is a `BudgetError`
+        (strict), or the image is coded with the map of round 1's first slope (t = 0) and is the one stream that may
+        exceed its budget.
+    Size of a candidate.  `image_stream_bytes(region_image_fixed_bytes(header), lz, ly)` from the chunk lengths the
+        coder reports; the map travels raw in the header, so the fixed part does not depend on the map.
+The streams are ordinary "ICRR" streams: byte for byte what `set_quality_map(map)` followed by `compress_each` writes.
+
 Encode-time latent refinement (`Compressor2018.compress_each_refined`): the rule
 ---------------------------------------------------------------------------------
 The decoder's inputs stay fixed: the weights and the hyper-latent, and so (sigma, mu).  Only the integers of y change,
@@ -790,6 +814,50 @@ def image_stream_bytes(fixed, *lens):
     """len() of a per-image stream whose `*_image_fixed_bytes` is `fixed` and whose chunk-length tables are `lens`:
     the fixed part counts every chunk's 256 bytes of lane states, the lengths count them again."""
     return int(fixed) + sum(int(np.asarray(l, dtype=np.int64).sum()) - CHUNK_HEAD * len(l) for l in lens)
+
+
+# ---- a quality map under a byte budget: the allocation rule of `compress_each_map_to` (the docstring's section)
+MAP_MAX_LEVELS = 16        # the levels one allocation chooses among (ic_block_allocate)
+
+
+def map_level_codes(S):
+    """The codes of the S integer levels, [quality_code(l, S) for l = 0 .. S-1]: what a map chosen by the allocation
+    rule holds."""
+    return [quality_code(l, S) for l in range(_check_levels(S))]
+
+
+def map_weight(lam, channels):
+    """float32(lam / channels) as a Python float: the weight w of J = B + w D for a distortion weight `lam` (the
+    model's `loss_weight(t)`) and an image of `channels` channels."""
+    if isinstance(channels, bool) or int(channels) != channels or channels < 1:
+        raise ValueError(f"codec: an image has at least 1 channel, got {channels!r}")
+    w = float(np.float32(float(lam) / int(channels)))
+    if not (math.isfinite(w) and w >= 0.0):
+        raise ValueError(f"codec: the weight of an allocation is finite and >= 0, got {lam!r} / {channels!r}")
+    return w
+
+
+def map_allocate(bits, sse, w):
+    """The level of every block at the weight w: bits, sse (L, nb) float32 tables -> (nb,) uint8, by the allocation
+    rule: J[l] = fadd(bits[l], fmul(w, sse[l])) in float32, l scanned ascending from best = 0 and replacing best iff
+    J[l] < J[best] (strict: a tie keeps the lower level, a NaN never wins)."""
+    bits, sse = np.asarray(bits), np.asarray(sse)
+    if bits.dtype != np.float32 or sse.dtype != np.float32 or bits.ndim != 2 or bits.shape != sse.shape:
+        raise ValueError(f"codec: the tables are float32 (levels, blocks) arrays of one shape, got {bits.dtype} "
+                         f"{bits.shape} and {sse.dtype} {sse.shape}")
+    if not 2 <= bits.shape[0] <= MAP_MAX_LEVELS or bits.shape[1] < 1:
+        raise ValueError(f"codec: an allocation chooses among 2 .. {MAP_MAX_LEVELS} levels for at least 1 block, got "
+                         f"{bits.shape}")
+    w = np.float32(w)
+    if not (np.isfinite(w) and w >= 0):
+        raise ValueError(f"codec: the weight of an allocation is finite and >= 0, got {w!r}")
+    with np.errstate(all="ignore"):
+        J = bits + w * sse                   # one float32 product, then one float32 sum, per element
+    best, best_j = np.zeros(bits.shape[1], dtype=np.uint8), J[0].copy()
+    for l in range(1, bits.shape[0]):
+        take = J[l] < best_j
+        best[take], best_j[take] = l, J[l][take]
+    return best
 
 
 # ---- region containers "ICRM" (batch) and "ICRR" (per image): the gained streams with a quality per 64 x 64 block

@@ -2002,6 +2002,128 @@ std::tuple<Tensor, std::vector<int64_t>> transcode_requant_seg_meta(const Tensor
   return {symbols_out(mu2), std::vector<int64_t>(img.size(), 0)};
 }
 
+// ---------------------------------------------------------------- a quality map under a byte budget (imgcomp_alloc)
+// bits, sse (N, L, nb) contiguous; img, w: the image and the weight of every candidate; codes: the code of every level
+void check_alloc_shapes(const Tensor& bits, const Tensor& sse, at::IntArrayRef img, at::ArrayRef<double> w,
+                        at::IntArrayRef codes) {
+  const int64_t M = (int64_t)img.size();
+  TORCH_CHECK(bits.dim() == 3 && bits.numel() > 0 && bits.size(1) >= 2 && bits.size(1) <= 16,
+              "imgcomp_alloc: the tables must be non-empty (N, 2 .. 16 levels, blocks) tensors, got ", bits.sizes());
+  TORCH_CHECK(sse.sizes() == bits.sizes(), "imgcomp_alloc: the two tables must share a shape, got ", bits.sizes(), " and ",
+              sse.sizes());
+  TORCH_CHECK(M >= 1 && M <= 65535 && (int64_t)w.size() == M, "imgcomp_alloc: ", M, " images and ", w.size(),
+              " weights do not make 1 .. 65535 candidates");
+  TORCH_CHECK((int64_t)codes.size() == bits.size(1), "imgcomp_alloc: ", codes.size(), " codes for ", bits.size(1), " levels");
+}
+
+std::tuple<Tensor, Tensor, Tensor> alloc_out(const Tensor& bits, int64_t M) {
+  const auto bytes = bits.options().dtype(at::kByte);
+  return {at::empty({M, bits.size(2)}, bytes), at::empty({M, bits.size(2)}, bytes),
+          at::empty({2, M}, bits.options().dtype(at::kDouble))};
+}
+
+std::tuple<Tensor, Tensor, Tensor> alloc_block_allocate(const Tensor& bits, const Tensor& sse, at::IntArrayRef img,
+                                                        at::ArrayRef<double> w, at::IntArrayRef codes) {
+  check_operand(bits, "bits");
+  check_operand(sse, "sse");
+  check_alloc_shapes(bits, sse, img, w, codes);
+  TORCH_CHECK(bits.is_contiguous() && sse.is_contiguous(), "imgcomp_alloc: the tables must be contiguous");
+  TORCH_CHECK(bits.device() == sse.device(), "imgcomp_alloc: the tables must be on one device");
+  const int64_t M = (int64_t)img.size(), N = bits.size(0), L = bits.size(1);
+  TORCH_CHECK(N <= 65535, "imgcomp_alloc: the tables are too large: ", bits.sizes());
+  std::vector<int> im;
+  std::vector<float> wf;
+  std::vector<unsigned char> lc;
+  for (int64_t m = 0; m < M; ++m) {
+    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_alloc: candidate ", m, " names image ", img[m], " of ", N);
+    const float v = (float)w[m];
+    TORCH_CHECK_VALUE(std::isfinite(v) && v >= 0.0f, "imgcomp_alloc: the weight of candidate ", m, " must be finite and "
+                      ">= 0, got ", w[m]);
+    im.push_back((int)img[m]);
+    wf.push_back(v);
+  }
+  for (int64_t l = 0; l < L; ++l) {
+    TORCH_CHECK_VALUE(codes[l] >= 0 && codes[l] <= 255, "imgcomp_alloc: the code of level ", l, " must be in 0 .. 255, got ",
+                      codes[l]);
+    lc.push_back((unsigned char)codes[l]);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(bits.device());
+  auto [ranks, out_codes, sums] = alloc_out(bits, M);
+  Tensor cand = at::empty({2 * M}, bits.options().dtype(at::kInt));   // the images, then the weights
+  check_rc(ic_block_allocate(bits.data_ptr<float>(), sse.data_ptr<float>(), (int)N, (int)L, bits.size(2), (int)M, im.data(),
+                             wf.data(), lc.data(), cand.data_ptr<int>(), ranks.data_ptr<uint8_t>(),
+                             out_codes.data_ptr<uint8_t>(), sums.data_ptr<double>(), stream_of(bits)),
+           "block_allocate");
+  return {ranks, out_codes, sums};
+}
+
+std::tuple<Tensor, Tensor, Tensor> alloc_block_allocate_meta(const Tensor& bits, const Tensor& sse, at::IntArrayRef img,
+                                                             at::ArrayRef<double> w, at::IntArrayRef codes) {
+  check_alloc_shapes(bits, sse, img, w, codes);
+  return alloc_out(bits, (int64_t)img.size());
+}
+
+// y (N, Hm, Wm, C) contiguous, read in place; g (R, C); rank: uint8 (M, ceil(Hm / 2^shift), ceil(Wm / 2^shift)); mu: the
+// M candidates' means back to back, each an image of y's size; img: the image of every candidate
+void check_alloc_symbolize_shapes(const Tensor& y, const Tensor& g, const Tensor& rank, const Tensor& mu,
+                                  at::IntArrayRef img, int64_t shift) {
+  const int64_t M = (int64_t)img.size();
+  TORCH_CHECK_VALUE(shift >= 0 && shift <= 6, "imgcomp_alloc: a block is 2^shift positions wide, shift in 0 .. 6, got ",
+                    shift);
+  TORCH_CHECK(y.dim() == 4 && y.numel() > 0, "imgcomp_alloc: y must be a non-empty (N, Hm, Wm, C) tensor, got ", y.sizes());
+  TORCH_CHECK(g.dim() == 2 && g.size(1) == y.size(3) && g.size(0) >= 1 && g.size(0) <= 256, "imgcomp_alloc: the gains ",
+              g.sizes(), " must be (1 .. 256, C) for y ", y.sizes());
+  TORCH_CHECK(M >= 1 && M <= 65535, "imgcomp_alloc: ", M, " candidates (1 .. 65535)");
+  TORCH_CHECK(rank.scalar_type() == at::kByte && rank.dim() == 3 && rank.size(0) == M &&
+                  rank.size(1) == map_extent(y.size(1), shift) && rank.size(2) == map_extent(y.size(2), shift),
+              "imgcomp_alloc: the rank map ", rank.sizes(), " must be uint8 (", M, ", ", map_extent(y.size(1), shift), ", ",
+              map_extent(y.size(2), shift), ") for y ", y.sizes(), " at shift ", shift);
+  TORCH_CHECK(mu.numel() == M * (y.numel() / y.size(0)), "imgcomp_alloc: mu (", mu.numel(), " values) must hold ", M,
+              " images of ", y.numel() / y.size(0), " values");
+}
+
+std::tuple<Tensor, std::vector<int64_t>> alloc_block_gain_symbolize_seg(const Tensor& y, const Tensor& g, const Tensor& rank,
+                                                                        const Tensor& mu, at::IntArrayRef img,
+                                                                        int64_t shift) {
+  check_operand(y, "y");
+  check_operand(g, "g");
+  check_operand(mu, "mu");
+  TORCH_CHECK(rank.is_cuda(), "imgcomp: the rank map must be on a ROCm device, got ", rank.device());
+  check_alloc_symbolize_shapes(y, g, rank, mu, img, shift);
+  TORCH_CHECK(y.is_contiguous() && g.is_contiguous() && rank.is_contiguous() && mu.is_contiguous(),
+              "imgcomp_alloc: y, g, the rank map and mu must be contiguous");
+  TORCH_CHECK(y.device() == g.device() && y.device() == mu.device() && y.device() == rank.device(),
+              "imgcomp_alloc: y, g, the rank map and mu must be on one device");
+  const int64_t M = (int64_t)img.size(), N = y.size(0);
+  TORCH_CHECK(N <= 65535 && y.numel() / N <= INT_MAX, "imgcomp_alloc: y is too large: ", y.sizes());
+  std::vector<int> im;
+  for (int64_t m = 0; m < M; ++m) {
+    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_alloc: candidate ", m, " names image ", img[m], " of ", N);
+    im.push_back((int)img[m]);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor sym = symbols_out(mu);
+  Tensor kd = at::empty({2 * M}, y.options().dtype(at::kInt));   // the maxima, then the images
+  std::vector<int> kmax((size_t)M, 0);
+  const int rc = ic_block_gain_symbolize_seg(y.data_ptr<float>(), (int)N, (int)y.size(1), (int)y.size(2), (int)y.size(3),
+                                             g.data_ptr<float>(), (int)g.size(0), rank.data_ptr<uint8_t>(), (int)shift,
+                                             mu.data_ptr<float>(), (int)M, im.data(), kd.data_ptr<int>() + M,
+                                             sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(y));
+  if (rc == IC_ERR_ARG)
+    for (int64_t m = 0; m < M; ++m)
+      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_alloc: candidate ", m, " (image ", img[m],
+                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, "block_gain_symbolize_seg");
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
+std::tuple<Tensor, std::vector<int64_t>> alloc_block_gain_symbolize_seg_meta(const Tensor& y, const Tensor& g,
+                                                                             const Tensor& rank, const Tensor& mu,
+                                                                             at::IntArrayRef img, int64_t shift) {
+  check_alloc_symbolize_shapes(y, g, rank, mu, img, shift);
+  return {symbols_out(mu), std::vector<int64_t>(img.size(), 0)};
+}
+
 // ---------------------------------------------------------------- encode-time latent refinement (imgcomp_refine)
 // The latent is (N, *, C) contiguous (channels-last storage); v, m and u are updated in place.  Nothing here copies to
 // the host or waits for the stream.  Inference only: no autograd node.
@@ -2704,3 +2826,20 @@ TORCH_LIBRARY(imgcomp_transcode, m) {
 TORCH_LIBRARY_IMPL(imgcomp_transcode, CUDA, m) { m.impl("requant_seg", transcode_requant_seg); }
 
 TORCH_LIBRARY_IMPL(imgcomp_transcode, Meta, m) { m.impl("requant_seg", transcode_requant_seg_meta); }
+
+// Choosing a quality map under a byte budget (RegionGainedMeanScaleCompressor2018.compress_each_map_to): additive, in a
+// namespace of its own.  Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_alloc, m) {
+  m.def("block_allocate(Tensor bits, Tensor sse, int[] img, float[] w, int[] codes) -> (Tensor, Tensor, Tensor)");
+  m.def("block_gain_symbolize_seg(Tensor y, Tensor g, Tensor rank, Tensor mu, int[] img, int shift) -> (Tensor, int[])");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_alloc, CUDA, m) {
+  m.impl("block_allocate", alloc_block_allocate);
+  m.impl("block_gain_symbolize_seg", alloc_block_gain_symbolize_seg);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_alloc, Meta, m) {
+  m.impl("block_allocate", alloc_block_allocate_meta);
+  m.impl("block_gain_symbolize_seg", alloc_block_gain_symbolize_seg_meta);
+}

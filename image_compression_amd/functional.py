@@ -1123,6 +1123,45 @@ def block_mse(a, b, w, idx):
     return BlockMSEFn.apply(a, b, w, idx)
 
 
+# ============================================================== a quality map under a byte budget
+def block_allocate(bits, sse, img, w, codes):
+    """The per-block level choice of M candidates by the allocation rule of codec.py: bits, sse (N, L, nb) the fp32
+    tables of N images at L levels; candidate m is image img[m] at the weight w[m] (finite, >= 0, a float32 value);
+    codes: the code of every level -> (ranks uint8 (M, nb): the chosen level of every block, codes uint8 (M, nb): its
+    code, sums float64 (2, M): the chosen bits and the chosen sse of every candidate, in a fixed order).  On the
+    device, no copy to the host (torch.ops.imgcomp_alloc.block_allocate).  Inference only."""
+    _lib.require_device(bits, sse)
+    _inference_only("block_allocate", bits=bits, sse=sse)
+    return _lib.alloc_ops().block_allocate(bits.detach().contiguous(), sse.detach().contiguous(), [int(i) for i in img],
+                                           [float(v) for v in w], [int(k) for k in codes])
+
+
+def block_gain_symbolize_seg(y, g, rank, mean, img, shift=2):
+    """`gain_symbolize_seg` with a gain row per block: candidate m is image img[m] of y (N, C, H, W), position (i, j)
+    scaled by the row rank[m, i >> shift, j >> shift] of g (R, C) and coded about mean[m] of mean (M, C, H, W); rank is
+    uint8 (M, ceil(H / 2^shift), ceil(W / 2^shift)) on the device -> (int32 symbols of the M candidates back to back,
+    each in (i, j, c) order, [kmax of candidate m]).  Bit for bit `block_scale` then `symbolize_mean_seg` on the
+    gathered batch y[img], which is never formed (torch.ops.imgcomp_alloc.block_gain_symbolize_seg).  Inference only;
+    ValueError naming the candidate whose symbols exceed the coder's limit."""
+    _lib.require_device(y, g, mean)
+    img, shift = [int(i) for i in img], int(shift)
+    if y.dim() != 4 or g.dim() != 2 or g.shape[1] != y.shape[1] or not 1 <= g.shape[0] <= 256:
+        raise ValueError(f"the gains {tuple(g.shape)} must be (1 .. 256, C) for a tensor of shape {tuple(y.shape)}")
+    if not 0 <= shift <= 6:
+        raise ValueError(f"a block is 2^shift positions wide, shift in 0 .. 6, got {shift}")
+    rank = _block_map(rank, y.device)
+    want = (len(img), -(-y.shape[2] >> shift), -(-y.shape[3] >> shift))
+    if tuple(rank.shape) != want:
+        raise ValueError(f"the rank map {tuple(rank.shape)} must be {want} for {len(img)} candidates of a tensor of shape "
+                         f"{tuple(y.shape)} at shift {shift}")
+    if tuple(mean.shape) != (len(img), *y.shape[1:]):
+        raise ValueError(f"the mean {tuple(mean.shape)} must hold {len(img)} candidates of shape {tuple(y.shape[1:])}")
+    _inference_only("block_gain_symbolize_seg", y=y, g=g, mean=mean)
+    sym, kmax = _lib.alloc_ops().block_gain_symbolize_seg(_to_last(y.detach()), g.detach().contiguous(), rank,
+                                                          _to_last(mean.detach()), img, shift)
+    return sym, [int(k) for k in kmax]
+
+
 # ============================================================== rate and distortion maps
 def _map_operand(t, who, what):
     """A map kernel's operand: fp32 (N, C, H, W) on the device; every image dense channels-last or dense NCHW storage

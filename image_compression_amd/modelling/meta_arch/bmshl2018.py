@@ -830,8 +830,6 @@ class Compressor2018(nn.Module):
         H, W = _codec.padded_size(h, w)
         self._check_call(N, H, W, who)
         self._clear_reparameterised()
-        y_shift, z_shift = ((_codec.MAP_BLOCK // d).bit_length() - 1 for d in (_codec.Y_DOWN, _codec.Z_DOWN))
-        em = self.entropy_model
         with torch.no_grad():
             xp = x
             if (H, W) != (h, w):
@@ -840,20 +838,30 @@ class Compressor2018(nn.Module):
             try:
                 self._begin_call(N, H, W, x.device, who)
                 y = self.analysis_transform(xp)
-                z = self._hyper_gain(self.prior_analysis(self._hyper_input(y)))
-                # the factorized model's (rint(z), p_z) without its loss: p_z in z's own logical shape
-                z_hat, p_z = factorized(z, em._cdf_estimator.flat_params(), False, None, em._cdf_estimator.dims, em.bin)
-                y_hat, p_y = self._forward_y(self._latent_gain(y), *self._prior(self._hyper_ungain(z_hat)))
-                if (H, W) == (h, w):
-                    x_hat = self._reconstruct(self._latent_ungain(y_hat))
-                else:
-                    x_hat = _lib.stream_ops().crop_clamp(self.synthesis_transform(self._latent_ungain(y_hat)), h, w)
+                return self._rate_distortion_from(x, y, self.prior_analysis(self._hyper_input(y)), likelihoods)
             finally:
                 self._end_call()
-            bits_y = block_bits(p_y, y_shift)
-            bits_z = block_bits(p_z, z_shift)
-            bits = block_bits(p_z, z_shift, add=bits_y)
-            sse = block_sse(x, x_hat, (_codec.MAP_BLOCK).bit_length() - 1)
+
+    def _rate_distortion_from(self, x, y, z, likelihoods=False):
+        """The RDMap of `rate_distortion_map` from y = g_a(padded x) and z = h_a(y) as they come out of the transforms,
+        neither of which depends on the quality: the rest of the eval pass and the four map kernels, under the gain
+        state the caller has set up (`_begin_call`).  x is the unpadded batch."""
+        h, w = x.shape[2:]
+        H, W = _codec.padded_size(h, w)
+        y_shift, z_shift = ((_codec.MAP_BLOCK // d).bit_length() - 1 for d in (_codec.Y_DOWN, _codec.Z_DOWN))
+        em = self.entropy_model
+        z = self._hyper_gain(z)
+        # the factorized model's (rint(z), p_z) without its loss: p_z in z's own logical shape
+        z_hat, p_z = factorized(z, em._cdf_estimator.flat_params(), False, None, em._cdf_estimator.dims, em.bin)
+        y_hat, p_y = self._forward_y(self._latent_gain(y), *self._prior(self._hyper_ungain(z_hat)))
+        if (H, W) == (h, w):
+            x_hat = self._reconstruct(self._latent_ungain(y_hat))
+        else:
+            x_hat = _lib.stream_ops().crop_clamp(self.synthesis_transform(self._latent_ungain(y_hat)), h, w)
+        bits_y = block_bits(p_y, y_shift)
+        bits_z = block_bits(p_z, z_shift)
+        bits = block_bits(p_z, z_shift, add=bits_y)
+        sse = block_sse(x, x_hat, (_codec.MAP_BLOCK).bit_length() - 1)
         return RDMap(bits_y, bits_z, bits, sse, block_pixels(h, w), x_hat, *((p_y, p_z) if likelihoods else ()))
 
     def _reconstruct_each(self, y_hat, hs):

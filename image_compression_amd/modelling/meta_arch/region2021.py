@@ -22,7 +22,13 @@ losses["MSE"] the plain mean (the kernel's second output).  With `sample_quality
 forward draws one integer level per block, independent and uniform, from the CPU generator seeded with cfg.SEED
 (`last_quality`: the code map; no device draw, the Philox order z, then y is unchanged); otherwise it uses the map
 that was set, or the uniform map of `quality`.  H and W must be multiples of 64 in training mode.  The map changes on
-the host every step, which is why TrainStep(graph=True) refuses this model (`graph_refusal`)."""
+the host every step, which is why TrainStep(graph=True) refuses this model (`graph_refusal`).
+
+Budget.  `compress_each_map_to(x, budgets)` chooses the map of every image so that its stream holds at most its budget
+of bytes: per block the level that minimises bits + w sse on the tables of `rate_distortion_tables` (the allocation
+rule of codec.py: an estimate that steers), at the slope the search rule of codec.py finds on sizes the coder itself
+reports (exact), every candidate map of every image allocated, symbolised and measured on the device from one pass of
+g_a and h_a.  It neither reads nor changes `quality` and `quality_map`."""
 import numpy as np
 import torch
 
@@ -195,8 +201,152 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
         return super().compress_each(x, steps_per_chunk)
 
     def compress_each_to(self, x, budgets, steps_per_chunk=1024, candidates=8, rounds=2, strict=True):
-        raise ValueError("compress_each_to searches one quality per image: a byte budget for a quality map is not built; "
-                         "use GainedMeanScaleCompressor2018 for budgets")
+        raise ValueError("compress_each_to searches one quality per image, not a quality map: use compress_each_map_to, "
+                         "which chooses the map for the budget, or GainedMeanScaleCompressor2018 for one quality")
+
+    # ---- a quality map under a byte budget: the allocation rule of codec.py, the search rule on the coder's own sizes
+    def _check_map_budget_call(self, x, budgets, steps_per_chunk, candidates, rounds, who):
+        if x.dim() != 4 or min(x.shape) < 1:
+            raise ValueError(f"{who}: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
+        if self.levels > _codec.MAP_MAX_LEVELS:
+            raise ValueError(f"{who}: the allocation chooses among at most {_codec.MAP_MAX_LEVELS} levels, this model "
+                             f"has {self.levels}")
+        return self._check_budget_args(who, x.shape[0], "images", budgets, steps_per_chunk, candidates, rounds)
+
+    def _level_tables(self, x, y, z):
+        """(bits, sse), each float32 (N, S, Hb Wb): `rate_distortion_map`'s `bits` and `sse` of the batch at every
+        integer level, from y = g_a(padded x) and z = h_a(y) computed once; x is the unpadded batch."""
+        N = x.shape[0]
+        H, W = _codec.padded_size(*x.shape[2:])
+        hb, wb = H // _codec.MAP_BLOCK, W // _codec.MAP_BLOCK
+        bits, sse = [], []
+        try:
+            for code in _codec.map_level_codes(self.levels):
+                self._use_map(np.full((N, hb, wb), code, dtype=np.uint8), x.device)
+                rd = self._rate_distortion_from(x, y, z)
+                bits.append(rd.bits.reshape(N, hb * wb))
+                sse.append(rd.sse.reshape(N, hb * wb))
+        finally:
+            self._clear()
+        return torch.stack(bits, dim=1), torch.stack(sse, dim=1)
+
+    @torch.no_grad()
+    def rate_distortion_tables(self, x):
+        """x (N, 3, h, w), any h, w >= 1 -> (bits, sse), each float32 (N, S, Hb Wb) on the device: the tables the
+        allocation rule of codec.py reads, bit for bit the `bits` and `sse` of `rate_distortion_map(x)` after
+        `set_quality(l)` for l = 0 .. S-1, from one pass of g_a and h_a.  Eval mode; `quality` and `quality_map` are
+        neither read nor changed."""
+        who = "rate_distortion_tables"
+        if self.training:
+            raise RuntimeError(f"{who} runs in eval mode only: call model.eval() first")
+        if x.dim() != 4 or min(x.shape) < 1:
+            raise ValueError(f"{who}: image batch {tuple(x.shape)} must be (N, C, h, w) with h, w >= 1")
+        self._codable_each()
+        xp, _ = self._pad_each(x)
+        y = self.analysis_transform(xp)
+        return self._level_tables(x, y, self.prior_analysis(self._hyper_input(y)))
+
+    @torch.no_grad()
+    def compress_each_map_to(self, x, budgets, steps_per_chunk=1024, candidates=8, rounds=2, strict=True):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1, and `budgets` (one positive int, or N of them: bytes of the whole
+        stream, header and map included) -> (a list of N "ICRR" streams, their quality maps: uint8 (Hb, Wb) arrays, the
+        float32 slopes the maps were allocated at): for every image the map the allocation rule of codec.py gives at
+        the slope its search rule chooses for the budget among `rounds` rounds of `candidates` slopes, so that
+        len(stream) <= budget.  A stream is byte for byte what `set_quality_map(map)` and `compress_each` write for
+        the image.  `quality` and `quality_map` are neither read nor changed.
+
+        What is exact and what is an estimate: the per-block tables (`rate_distortion_tables`: the estimated bits and
+        the squared error of every block at every integer level) only steer where the bits go, and a map is the exact
+        minimiser of their tabulated sum and nothing more; the budget is enforced on the sizes the coder itself
+        reports for every candidate map (`measure_seg`), h_s run image by image as the decoder runs it.
+
+        g_a and h_a run once; the S passes of h_s and g_s for the tables run at batch N.  All candidates of all images
+        of a round are allocated, symbolised and measured by one set of launches, the maps staying on the device; one
+        small copy of the chunk lengths comes back per round.  Only the N chosen candidates are coded, and their maps
+        copied to the host once.
+
+        An image that fits at no slope of round 1: codec.BudgetError (a ValueError with .image, .budget, .smallest) in
+        front of any packing; with strict=False it is coded with the map of slope 0 and is the one stream that may
+        exceed its budget."""
+        from ...functional import block_allocate, block_gain_symbolize_seg, measure_seg
+        from ..blocks.entropy_model import symbolize_seg, symbols_as_tensor, table_pool
+        who = "compress_each_map_to"
+        budgets = self._check_map_budget_call(x, budgets, steps_per_chunk, candidates, rounds, who)
+        self._codable_each()
+        em, cm, R, S = self.entropy_model, self.conditional_model, int(steps_per_chunk), self.levels
+        channels = x.shape[1]
+        xp, (N, h, w, H, W) = self._pad_each(x)
+        hb, wb = H // _codec.MAP_BLOCK, W // _codec.MAP_BLOCK
+        y = self.analysis_transform(xp)
+        z = self.prior_analysis(self._hyper_input(y))
+        bits, sse = self._level_tables(x, y, z)
+        level_codes = _codec.map_level_codes(S)
+        z_tables, y_tables = {}, {}     # one table per K and tensor kind for the whole call
+
+        def tables_z(K):
+            if K not in z_tables:
+                z_tables[K] = em.tables(K)
+            return z_tables[K]
+
+        def tables_y(K):
+            if K not in y_tables:
+                y_tables[K] = cm.tables(K, y.device)
+            return y_tables[K]
+
+        try:
+            # one gain row per level: a row is a function of its code alone, so level indices serve as ranks
+            self._use([_codec.code_quality(k, S) for k in level_codes])
+            g_y, _, g_z, g_inv_z = self._gains
+            self._codes = np.zeros((1, hb, wb), dtype=np.uint8)     # the fixed part does not depend on the map
+            fixed = _codec.region_image_fixed_bytes(self._header(1, H, W, y, z, R, 0, 0, (h, w)))
+
+            def measure(cands):
+                img, ts = [n for n, _ in cands], [t for _, t in cands]
+                M = len(cands)
+                ws = [_codec.map_weight(self.loss_weight(t), channels) for t in ts]
+                ranks, codes, _sums = block_allocate(bits, sse, img, ws, level_codes)
+                ranks = ranks.view(M, hb, wb)
+                try:
+                    zc = z[torch.as_tensor(img, device=z.device)]
+                    z_sym, kz = symbolize_seg(block_scale(zc, g_z, ranks, 0))
+                    z_hat = block_scale(symbols_as_tensor(z_sym.to(torch.float32), (M, *z.shape[1:])), g_inv_z, ranks, 0)
+                    sigma, mean = self._prior_each(z_hat)
+                    y_sym, ky = block_gain_symbolize_seg(y, g_y, ranks, mean, img, 2)
+                except ValueError as e:
+                    raise ValueError(f"{who}: among the candidates (image, slope) {cands}: {e}") from None
+                rows = cm.scale_rows(sigma.expand_as(mean))
+                lz = measure_seg(z_sym, M, None, em.channels, *table_pool(tables_z, kz), R)
+                ly = measure_seg(y_sym, M, rows, 0, *table_pool(tables_y, ky), R)
+                lens = torch.cat([lz, ly]).cpu().numpy().astype(np.int64)    # the one D2H copy of the round
+                lz, ly = lens[:lz.numel()].reshape(M, -1), lens[lz.numel():].reshape(M, -1)
+                size = [_codec.image_stream_bytes(fixed, lz[m], ly[m]) for m in range(M)]
+                nz, ny = z_sym.numel() // M, y_sym.numel() // M
+
+                def keep(m):
+                    return (z_sym[m * nz:(m + 1) * nz].clone(), kz[m], y_sym[m * ny:(m + 1) * ny].clone(), ky[m],
+                            sigma[m:m + 1].clone(), mean[m:m + 1].clone(), size[m], codes[m].clone())
+                return size, keep
+
+            measured = {n: {} for n in range(N)}   # slope -> bytes, everything measured for the image so far
+            todo = {n: _codec.budget_grid(S, candidates) for n in range(N)}
+            chosen, kept = self._budget_rounds(dict(enumerate(budgets)), todo, measured, candidates, rounds, strict, measure)
+            chosen, kept = [chosen[n] for n in range(N)], [kept[n] for n in range(N)]
+            self._codes = torch.stack([k[7] for k in kept]).cpu().numpy().reshape(N, hb, wb)    # the maps, once
+            z_sym, y_sym = (torch.cat([k[i] for k in kept]) for i in (0, 2))
+            sigma, mean = (torch.cat([k[i] for k in kept]) for i in (4, 5))
+            kz, ky = ([k[i] for k in kept] for i in (1, 3))
+            sz = em.encode_symbols_seg(z_sym, kz, R)
+            sy = cm.encode_symbols_seg(y_sym, ky, sigma.expand_as(y), R, mean=mean)
+            streams = [self._pack_image(self._header(1, H, W, y, z, R, kz[n], ky[n], (h, w), n),
+                                        sz[n][1], sy[n][1], sz[n][0], sy[n][0]) for n in range(N)]
+            maps = [self._codes[n].copy() for n in range(N)]
+        finally:
+            self._clear()
+        for n, s in enumerate(streams):
+            if len(s) != kept[n][6]:
+                raise RuntimeError(f"{who}: the stream of image {n} at slope {chosen[n]} holds {len(s)} bytes, "
+                                   f"{kept[n][6]} were measured")
+        return streams, maps, chosen
 
     def _transcode_qualities(self, qualities, M, who):
         raise ValueError(f"{who}: the streams of RegionGainedMeanScaleCompressor2018 carry a quality map: requantizing a "

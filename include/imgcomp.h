@@ -792,6 +792,39 @@ int ic_requant_seg(const float* r, const float* mu1, long long N, long long P, i
                    const float* mu2, int nseg, const int* img, int* img_dev, int* sym, int* kmax_dev, int* kmax_host,
                    void* stream);
 
+/* ---- choosing a quality map under a byte budget (additive to version 4;
+ *      RegionGainedMeanScaleCompressor2018.compress_each_map_to).  The per-block level choice of many (image, weight)
+ *      candidates in one launch, and the symbols of y for many (image, level map) candidates in one launch.
+ *      IC_ERR_ARG before any launch for a null pointer or anything the text below excludes; neither allocates; no
+ *      floating-point atomics. ---- */
+/* bits, sse: the tables (N, L, nb) dense, fp32: level l of image n is nb per-block values (the maps of ic_block_bits /
+ * ic_block_sse at that level), 1 <= N <= 65535, 2 <= L <= 16, nb >= 1.  Candidate m of M (1 .. 65535) names its image
+ * img[m] in [0, N) and its weight w[m], finite and >= 0 (host arrays, checked, then copied to cand_dev: M ints and M
+ * floats, 8 M bytes on the device).  For block b of candidate m, every operation one fp32 operation rounded once:
+ *     J[l] = bits[img[m]][l][b] + w[m] * sse[img[m]][l][b];  best = 0, then l = 1 .. L-1 ascending replaces best iff
+ *     J[l] < J[best] (strict: a tie keeps the lower level, a NaN never wins)
+ *     ranks[m][b] = best;  codes[m][b] = level_codes[best]   (level_codes: L bytes on the host)
+ *     sums[0][m] = the sum over b of bits[img[m]][best(b)][b], sums[1][m] the same of sse, in fp64; sums is (2, M)
+ * The order of the sums is a function of nb alone: one HIP block of 256 threads per candidate, thread t adds the
+ * values of blocks t, t + 256, ... in ascending order, then partial[t] += partial[t + s] for s = 128, 64, ..., 1; two
+ * runs agree bit for bit.  Does not wait for its stream. */
+int ic_block_allocate(const float* bits, const float* sse, int N, int L, long long nb, int M, const int* img,
+                      const float* w, const unsigned char* level_codes, void* cand_dev, unsigned char* ranks,
+                      unsigned char* codes, double* sums, void* stream);
+/* ic_gain_symbolize_seg with a gain row per block: y the latent of N images, dense (N, Hm, Wm, C) storage, channel
+ * fastest, read in place; g (R, C), 1 <= R <= 256; rank: uint8 (nseg, ceil(Hm / 2^shift), ceil(Wm / 2^shift)) on the
+ * device, a rank >= R clamped to R - 1; candidate m of nseg (1 .. 65535) names its image img[m] in [0, N) (host array,
+ * checked, then copied to img_dev: nseg ints on the device), its rank map rank[m] and its mean mu[m] of mu (nseg, Hm,
+ * Wm, C):
+ *     sym[m][i][j][c] = the symbol of (y[img[m]][i][j][c] * g[rank[m][i >> shift][j >> shift]][c]) - mu[m][i][j][c]
+ * the product ic_block_scale's one fp32 multiplication, the difference and the symbol those of
+ * ic_codec_symbolize_mean_seg: bit for bit these two calls on the gathered batch y[img].  Hm Wm C < 2^31, shift in
+ * 0 .. 6.  kmax_dev / kmax_host as in ic_gain_symbolize_seg: the maximum |symbol| of every candidate, one copy of the
+ * nseg maxima and one wait for the stream, IC_ERR_ARG (with kmax_host filled) when any exceeds IC_CODEC_KMAX. */
+int ic_block_gain_symbolize_seg(const float* y, int N, int Hm, int Wm, int C, const float* g, int R,
+                                const unsigned char* rank, int shift, const float* mu, int nseg, const int* img,
+                                int* img_dev, int* sym, int* kmax_dev, int* kmax_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
