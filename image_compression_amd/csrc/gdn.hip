@@ -57,9 +57,16 @@ void gemm1x1(IgDesc& d, const ic_act* x, const ic_act* y) {
 }
 
 // y (and x) compact NHWC: the layout of the bf16 copies (ic_gdn_fwd_xb / ic_gdn_bwd_sum_xb)
+// (the stride of a dimension of size 1 multiplies no index: not compared, as in gdn_fused_ok)
 static bool compact_nhwc(const ic_act* a) {
-  return a->sc == 1 && a->sw == a->c && a->sh == (long long)a->w * a->c && a->sn == (long long)a->h * a->w * a->c &&
-         a->c % 8 == 0;
+  return a->sc == 1 && (a->w <= 1 || a->sw == a->c) && (a->h <= 1 || a->sh == (long long)a->w * a->c) &&
+         (a->n <= 1 || a->sn == (long long)a->h * a->w * a->c) && a->c % 8 == 0;
+}
+
+// b has a's layout: equal strides in every dimension above size 1 (the shapes are equal)
+static bool same_strides(const ic_act* a, const ic_act* b) {
+  return (a->n <= 1 || a->sn == b->sn) && (a->c <= 1 || a->sc == b->sc) && (a->h <= 1 || a->sh == b->sh) &&
+         (a->w <= 1 || a->sw == b->sw);
 }
 
 // yb (non-null): y's compact NHWC bf16 copy as well -- written by the fused bf16 kernel's epilogue, or
@@ -74,7 +81,7 @@ int gdn_fwd_impl(const ic_act* x, const float* gamma, const float* beta, int inv
   const bool split = (math & IC_MATH_SPLIT) && x->c % 32 == 0 && x->sc == 1 && x->c >= 64;
   // the workspace query answers for the general path (the fused one needs none)
   if (!need && (!split || x->c == 192) && gdn_fused_ok(x->data, y->data, norm, x->c, x->sc, x->sw, x->sh, x->sn, x->h, x->w, P) &&
-      x->sn == y->sn && x->sc == y->sc && x->sh == y->sh && x->sw == y->sw &&
+      same_strides(x, y) &&
       ((uintptr_t)gamma & 15) == 0) {
     const int mode = (math & IC_MATH_BF16) && split && x->c == 192 ? 2 : split ? 1 : 0;
     if (!norm && mode != 2) return IC_ERR_ARG;  // norm left out: the bf16 kernel only (ic_gdn_fwd_rn)
@@ -90,13 +97,14 @@ int gdn_fwd_impl(const ic_act* x, const float* gamma, const float* beta, int inv
   d.a_op = AOP_SQUARE;
   d.aux0 = x->data;
   d.aux_out = norm;
-  d.x3 = split ? 1 : 0;
+  // the split kernel has no gather form (ig_run refuses the pair): a misaligned or size-1-strided x runs fp32
+  d.x3 = split && !d.generic ? 1 : 0;
   const size_t part = ig_plan(d);
   const size_t wpb = (size_t)d.Npad * d.Kc * (d.x3 ? 6 : 4);
   d.wplane = (long long)d.Npad * d.Kc;
   const size_t tot = ic_align(wpb, 256) + ic_align(part, 256);
   if (need) { *need = tot; return IC_OK; }
-  if (x->sn != y->sn || x->sc != y->sc || x->sh != y->sh || x->sw != y->sw) return IC_ERR_ARG;
+  if (!same_strides(x, y)) return IC_ERR_ARG;
   if (wsb < tot) return IC_ERR_WORKSPACE;
   Carve cv{(char*)ws, 0};
   float* wp = cv.take(wpb);
@@ -131,7 +139,7 @@ int gdn_bwd_impl(const ic_act* x, const float* norm, const float* dy, const floa
   // (per-block dgamma partials) is also reserved by the query below
   const size_t fused_ws = gdn_bwd_fused_ws(x->c, P);
   if (!need && gdn_fused_ok(x->data, dx->data, norm, x->c, x->sc, x->sw, x->sh, x->sn, x->h, x->w, P) &&
-      ((uintptr_t)dy & 15) == 0 && x->sn == dx->sn && x->sc == dx->sc && x->sh == dx->sh && x->sw == dx->sw &&
+      ((uintptr_t)dy & 15) == 0 && same_strides(x, dx) &&
       wsb >= fused_ws) {
     const int mode = (math & IC_MATH_BF16) && x->c == 192 ? 2 : (math & IC_MATH_SPLIT) ? 1 : 0;
     if (!norm && mode != 2) return IC_ERR_ARG;  // norm recomputed: the bf16 kernel only (ic_gdn_bwd_sum_rn)
@@ -167,7 +175,7 @@ int gdn_bwd_impl(const ic_act* x, const float* norm, const float* dy, const floa
                      ic_align(wpart, 256) + ic_align(cs, 256);
   if (need) { *need = tot > fused_ws ? tot : fused_ws; return IC_OK; }
   if (!dense_like(x)) return IC_ERR_ARG;
-  if (x->sn != dx->sn || x->sc != dx->sc || x->sh != dx->sh || x->sw != dx->sw) return IC_ERR_ARG;
+  if (!same_strides(x, dx)) return IC_ERR_ARG;
   if (wsb < tot) return IC_ERR_WORKSPACE;
   Carve cv{(char*)ws, 0};
   float* q = cv.take((size_t)n * 4);

@@ -1380,12 +1380,16 @@ int gdn_bwd_fused_launch(const float* x, const float* norm, const float* dy, con
 
 }  // namespace
 
-// NHWC-dense (channel stride 1, pixel stride C), 16-B aligned, C in {64,128,192}
+// NHWC-dense (channel stride 1, pixel stride C), 16-B aligned, C in {64,128,192}.  The stride of a dimension of
+// size 1 multiplies no index and may hold anything (a contiguous (n, C, 1, 1) tensor keeps strides (C, 1, 1, 1)
+// as channels-last): the kernels index [pixel][C], so only the dimensions above size 1 have to be dense.
 bool gdn_fused_ok(const float* x, const float* y, const float* norm, int C, long long sc, long long sw, long long sh,
                   long long sn, int H, int W, long long P) {
   if (!(C == 64 || C == 128 || C == 192)) return false;
-  if (sc != 1 || sw != C || sh != (long long)W * C || sn != (long long)H * W * C) return false;
-  if (P >= (1LL << 31) || P < 1) return false;
+  if (P >= (1LL << 31) || P < 1 || H < 1 || W < 1) return false;
+  const long long N = P / ((long long)H * W);
+  if (sc != 1 || (W > 1 && sw != C) || (H > 1 && sh != (long long)W * C) || (N > 1 && sn != (long long)H * W * C))
+    return false;
   auto a16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
   return a16(x) && a16(y) && a16(norm);
 }

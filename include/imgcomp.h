@@ -146,7 +146,9 @@ int ic_gdn_bwd(const ic_act* x, const float* norm, const float* dy, const float*
                void* stream);
 /* math = IC_MATH_SPLIT (C % 32 == 0, C >= 64, channel-contiguous): the forward runs in split arithmetic —
  * the fused kernel for NHWC-dense C = 192, otherwise the split implicit GEMM (x^2 squared in its staging,
- * the divide in its epilogue). */
+ * the divide in its epilogue) where x takes its fast form (16-byte aligned base and pixel strides), fp32 where
+ * not.  NHWC-dense: channel stride 1 and pixel stride C over every dimension above size 1 (the stride of a
+ * dimension of size 1 is not looked at, here and for the compact NHWC copies below). */
 size_t ic_gdn_fwd_ws_ex(const ic_act* x, int math);
 int ic_gdn_fwd_ex(const ic_act* x, const float* gamma, const float* beta, int inverse, const ic_act* y, float* norm,
                   int math, void* ws, size_t ws_bytes, void* stream);

@@ -352,6 +352,18 @@ def test_gdn_bwd_dx_column_sums(C, H, W, math):
     assert torch.equal(dx, dx2) and torch.equal(dg, dg2) and torch.equal(db, db2)
     ref = dx.double().sum(dim=(0, 2, 3))
     assert ((dxs.double() - ref).abs().max() / ref.abs().max()).item() < 1e-5
+    # and against float64 autograd of the same values (rows = pixels; tests/test_gdn_gpu.py holds every launch path)
+    xr = x.cpu().permute(0, 2, 3, 1).reshape(-1, C).double().requires_grad_(True)
+    gr = gamma.cpu().reshape(C, C).double().requires_grad_(True)
+    br = beta.cpu().double().requires_grad_(True)
+    nr = (xr * xr) @ gr.t() + br
+    (xr / nr.sqrt()).backward(dy.cpu().permute(0, 2, 3, 1).reshape(-1, C).double())
+    dxr = xr.grad.reshape(3, H, W, C).permute(0, 3, 1, 2)
+    assert_close(norm.cpu(), nr.detach().reshape(3, H, W, C).permute(0, 3, 1, 2), 1e-4, "norm")
+    assert_close(dx.cpu(), dxr, 1e-4, "dx")
+    assert_close(dg.cpu().reshape(C, C), gr.grad, 1e-4, "dgamma")
+    assert_close(db.cpu(), br.grad, 1e-4, "dbeta")
+    assert_close(dxs.cpu(), dxr.sum(dim=(0, 2, 3)), 1e-4, "dxsum")
 
 
 def test_conv_bias_from_gdn_column_sums():
