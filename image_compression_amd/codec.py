@@ -115,7 +115,8 @@ Gained containers (little endian): `GainedMeanScaleCompressor2018`, one network 
 The model carries four level tables t (S, C) -- gains of y and of z and their inverses -- and codes at a quality q
 in [0, S-1] held as float32.  The gain-vector rule, per table and channel c:
     s = min(int(floorf(q)), S - 2),  f = q - s,
-    a = fadd(fmul(1 - f, t[s][c]), fmul(f, t[s+1][c]))      (float32, each operation rounded once, none contracted)
+    a = fma(f, t[s+1][c], fmul(1 - f, t[s][c]))             (float32: 1 - f and the lower level's product rounded
+                                                             once each, the upper level's product fused with the sum)
     g[c] = 1.0f if a == 0 else expf(a)
 so an integer q gives exp(t[q]), the values between interpolate geometrically, and zero tables give gains of
 exactly 1.0.  With (g_y, g_y', g_z, g_z') the four vectors at q, every product one float32 multiplication per

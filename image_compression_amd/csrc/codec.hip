@@ -16,45 +16,25 @@
 #include <algorithm>
 #include <vector>
 
-#include "common.h"
-#include "codec_sym.h"
+#include "seg_symbolize.h"
 #include "codec_chunk.h"
-#include "../../include/imgcomp.h"
 
 namespace {
 
 constexpr int CODEC_KMAX = IC_CODEC_KMAX;            // 2K+1 <= 4095 counts of >= 1 fit 16 bits
 
 // ------------------------------------------------------------------ symbolize
-// q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and max|q| by one
-// integer atomic per block (integer max is order-independent: deterministic).
-// (symbol_of and block_max: codec_sym.h, shared with the mean-scale symbolizers of meancodec.hip)
-__global__ void codec_symbolize_k(const float* __restrict__ x, long long n, int* __restrict__ sym,
-                                  int* __restrict__ kmax) {
-  int m = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
-    const int k = symbol_of(x[i]);
-    sym[i] = k;
-    m = max(m, k < 0 ? -k : k);
+// q = rintf(x) (the value quant_k / cond_fwd_k mode 1 produce) as int32, and each segment's max|q|: seg_symbolize.h's
+// walk and driver over x itself
+struct PlainSrc {
+  const float* x;
+  __device__ __forceinline__ void bind(unsigned seg, long long len, long long, long long) { x += (long long)seg * len; }
+  template <class V>
+  __device__ __forceinline__ V at(long long i) const {
+    return load_as<V>(x, i);
   }
-  m = block_max(m);
-  if (threadIdx.x == 0) atomicMax(kmax, m);
-}
-
-// nseg segments of seg_len values back to back: blockIdx.y = segment, kmax[segment] = its max |q|
-__global__ void codec_symbolize_seg_k(const float* __restrict__ x, long long seg_len, int* __restrict__ sym,
-                                      int* __restrict__ kmax) {
-  const long long base = (long long)blockIdx.y * seg_len;
-  int m = 0;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < seg_len;
-       i += (long long)gridDim.x * blockDim.x) {
-    const int k = symbol_of(x[base + i]);
-    sym[base + i] = k;
-    m = max(m, k < 0 ? -k : k);
-  }
-  m = block_max(m);
-  if (threadIdx.x == 0) atomicMax(kmax + blockIdx.y, m);
-}
+  __device__ __forceinline__ void next() {}
+};
 
 // ------------------------------------------------------------------ scale index
 struct ScaleMids {
@@ -340,17 +320,8 @@ extern "C" {
 
 int ic_codec_symbolize(const float* x, long long n, int* sym, int* kmax_dev, int* kmax_host, void* stream) {
   if (!x || !sym || !kmax_dev || !kmax_host || n < 1) return IC_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(kmax_dev, 0, sizeof(int), st);
-  if (e != hipSuccess) return (int)e;
-  const int blocks = (int)std::min<long long>((n + 255) / 256, 1024);
-  hipLaunchKernelGGL(codec_symbolize_k, dim3(blocks), dim3(256), 0, st, x, n, sym, kmax_dev);
-  IC_CHECK_LAUNCH();
-  e = hipMemcpyAsync(kmax_host, kmax_dev, sizeof(int), hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return (int)e;
-  return *kmax_host > CODEC_KMAX ? IC_ERR_ARG : IC_OK;
+  return seg_symbolize(PlainSrc{x}, aligned16(x) && aligned16(sym), 1, n, nullptr, nullptr, sym, kmax_dev, kmax_host,
+                       (hipStream_t)stream);
 }
 
 int ic_codec_scale_index(const float* sigma, long long n, const float* mids, int L, unsigned char* rows,
@@ -456,19 +427,9 @@ int ic_codec_symbolize_seg(const float* x, int nseg, long long seg_len, int* sym
   if (!x || !sym || !kmax_dev || !kmax_host || nseg < 1 || nseg > 65535 || seg_len < 1 ||
       seg_len > 0x7fffffffffffffffll / nseg)
     return IC_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(kmax_dev, 0, sizeof(int) * nseg, st);
-  if (e != hipSuccess) return (int)e;
-  const int blocks = (int)std::min<long long>((seg_len + 255) / 256, 1024);
-  hipLaunchKernelGGL(codec_symbolize_seg_k, dim3(blocks, nseg), dim3(256), 0, st, x, seg_len, sym, kmax_dev);
-  IC_CHECK_LAUNCH();
-  e = hipMemcpyAsync(kmax_host, kmax_dev, sizeof(int) * nseg, hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return (int)e;
-  for (int s = 0; s < nseg; ++s)
-    if (kmax_host[s] > CODEC_KMAX) return IC_ERR_ARG;
-  return IC_OK;
+  // a segment starts at s * seg_len elements: 16-byte aligned for every s only when seg_len % 4 == 0
+  const bool vec = aligned16(x) && aligned16(sym) && (nseg == 1 || seg_len % 4 == 0);
+  return seg_symbolize(PlainSrc{x}, vec, nseg, seg_len, nullptr, nullptr, sym, kmax_dev, kmax_host, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1,6 +1,5 @@
-// What the symbolizers of the entropy coder share (codec.hip: rint(x); meancodec.hip: rint(y - mu)):
-// the clamp-and-NaN rule that turns a float into a symbol, and the block maximum behind the one
-// integer atomicMax per block.
+// The two device functions under the symbolizers' walk (seg_symbolize.h): the clamp-and-NaN rule that turns a
+// float into a symbol, and the block maximum behind the one integer atomicMax per block.
 #pragma once
 #include "common.h"
 

@@ -1,10 +1,11 @@
 // Gain units (Cui et al. 2021): per-channel gain vectors interpolated between S learnt levels, and the scaling of a
 // latent by them (ic_gain_vector*, ic_channel_scale*).
 //   * The gain-vector rule (codec.py states it for the container): for a table t (S, C) and a quality q held as
-//     fp32, s = min((int)floorf(q), S - 2), f = q - s, a = (1 - f) t[s][c] + f t[s+1][c] with the two products and
-//     the sum each rounded once (__fmul_rn / __fadd_rn: never contracted), g[c] = 1.0f where a == 0 and expf(a)
-//     elsewhere.  Both sides of the codec run this kernel on the fp32 quality the stream stores, so they hold the
-//     same gain bits; a model with zero tables has gains of exactly 1.0.
+//     fp32, s = min((int)floorf(q), S - 2), f = q - s, a = fma(f, t[s+1][c], fl((1 - f) t[s][c])): the two
+//     subtractions and the lower level's product rounded once each (fp_rn.h), the upper level's product fused with the
+//     sum and rounded once; g[c] = 1.0f where a == 0 and expf(a) elsewhere.  Both sides of the codec run this kernel on
+//     the fp32 quality the stream stores, so they hold the same gain bits; a model with zero tables has gains of
+//     exactly 1.0.  The fused step is written out (fmaf): the rule is the format's, not the compiler's choice.
 //   * out = x * g is one fp32 multiplication per element (__fmul_rn), the gain broadcast over the positions.
 //   * No floating-point atomics: every gradient sum runs in a fixed order (dtable: one thread per (s, c) over the
 //     qualities in ascending order; dg: per block over its positions, then one thread per (row, c) over the
@@ -15,6 +16,7 @@
 #include <algorithm>
 
 #include "common.h"
+#include "fp_rn.h"
 #include "../../include/imgcomp.h"
 
 namespace {
@@ -45,8 +47,7 @@ __global__ void __launch_bounds__(GN_THREADS) gain_vector_k(const float* __restr
   int s;
   float f;
   level_of(qs.q[k], S, s, f);
-  const float a = __fadd_rn(__fmul_rn(__fsub_rn(1.0f, f), table[(long long)s * C + c]),
-                            __fmul_rn(f, table[(long long)(s + 1) * C + c]));
+  const float a = fmaf(f, table[(long long)(s + 1) * C + c], mul_rn(__fsub_rn(1.0f, f), table[(long long)s * C + c]));
   out[i] = a == 0.0f ? 1.0f : expf(a);
 }
 

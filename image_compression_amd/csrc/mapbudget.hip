@@ -1,46 +1,28 @@
 // Choosing a quality map under a byte budget (RegionGainedMeanScaleCompressor2018.compress_each_map_to): the per-block
 // level choice of M candidate (image, weight) pairs in one launch (ic_block_allocate), and the symbols of y for M
 // candidate (image, level map) pairs in one launch (ic_block_gain_symbolize_seg).
-//   * The allocation is codec.py's rule: for block b of candidate m, J[l] = fadd(bits[img[m]][l][b], fmul(w[m],
-//     sse[img[m]][l][b])), each operation rounded once (mul_rn, add_rn below: compiled with contraction off), l scanned
-//     ascending from best = 0 and replaced iff J[l] < J[best] (strict: a tie keeps the lower level, a NaN never wins).
+//   * The allocation is codec.py's rule: for block b of candidate m, J[l] = add_rn(bits[img[m]][l][b], mul_rn(w[m],
+//     sse[img[m]][l][b])), each operation rounded once (fp_rn.h), l scanned ascending from best = 0 and replaced iff
+//     J[l] < J[best] (strict: a tie keeps the lower level, a NaN never wins).
 //   * The sums of the chosen bits and the chosen sse are fp64 in one fixed order, a function of nb alone: one HIP
 //     block of 256 threads per candidate, thread t adds blocks t, t + 256, ... ascending, then the 256 partial sums
 //     are folded in LDS, partial[t] += partial[t + s] for s = 128, 64, ..., 1.  No atomics.
-//   * The symbols are sym[m][i] = symbol_of(fsub(fmul(y[img[m]][i], g[rank[m][block(i)]][c(i)]), mu[m][i])): the
+//   * The symbols are sym[m][i] = symbol_of(sub_rn(mul_rn(y[img[m]][i], g[rank[m][block(i)]][c(i)]), mu[m][i])): the
 //     product is ic_block_scale's one fp32 multiplication, with its walk over (row, column, channel) and its clamp of
 //     a rank >= R to R - 1; the difference and the symbol are ic_codec_symbolize_mean_seg's: bit for bit those two
-//     calls on the gathered batch y[img], without the gather copy and without the scaled latent in memory.  kmax[m] is
-//     one integer atomicMax per block: order-independent, deterministic.  No floating-point atomics.
-// y, mu and sym are dense channels-last storage (Hm, Wm, C per image, channel fastest).  The symbolizer is grid-stride
-// and HBM-bound, as budget.hip and region.hip: 16-byte accesses when every pointer is 16-byte aligned and C % 4 == 0,
-// scalar accesses with the same arithmetic otherwise.  The tables of the allocation are a few kilobytes (S levels of
-// one value per 64 x 64 pixel block): scalar loads, coalesced along the blocks.
+//     calls on the gathered batch y[img], without the gather copy and without the scaled latent in memory.
+// y, mu and sym are dense channels-last storage (Hm, Wm, C per image, channel fastest).  The symbolizer is
+// seg_symbolize.h's walk and driver over a source whose cursor is (row, column, channel): 16-byte accesses when every
+// pointer is 16-byte aligned and C % 4 == 0.  The tables of the allocation are a few kilobytes (S levels of one value
+// per 64 x 64 pixel block): scalar loads, coalesced along the blocks.
 #include <algorithm>
 #include <cmath>
 
-#include "common.h"
-#include "codec_sym.h"
-#include "../../include/imgcomp.h"
-
-// A product and the sum that follows it, each rounded once.  The header's __fmul_rn followed by __fadd_rn / __fsub_rn
-// does not say that to the compiler: they are a plain product and a plain sum compiled under its default contraction,
-// and the pair becomes one v_fma_f32, one rounding instead of the two the rules state: a symbol or a level that
-// differs from the two separate kernels where the product is inexact and the sum lands on a tie (one symbol of y in
-// 2.4 million on the benchmark's images).  The three helpers below are compiled with contraction off, so neither
-// operation carries the flag that lets the backend fuse it; the disassembly of this file holds no fused multiply-add.
-#pragma clang fp contract(off)
+#include "seg_symbolize.h"
 
 namespace {
 
-__device__ __forceinline__ float mul_rn(float a, float b) { return a * b; }
-__device__ __forceinline__ float add_rn(float a, float b) { return a + b; }
-__device__ __forceinline__ float sub_rn(float a, float b) { return a - b; }
-
-typedef int intx4v __attribute__((ext_vector_type(4)));
-
-constexpr int MB_THREADS = 256;
-constexpr int MB_MAXBLOCKS = 1024;
+constexpr int MB_THREADS = 256;   // of the allocation: its fold in LDS is written for this many
 constexpr int MB_MAXLEVELS = 16;
 
 // the codes of the L <= 16 levels, eight to a word: level l is byte l & 7 of word l >> 3
@@ -97,49 +79,31 @@ __global__ void __launch_bounds__(MB_THREADS) block_allocate_k(const float* __re
   }
 }
 
-// blockIdx.y = candidate; one image is Hm * Wm * C elements (< 2^31: checked on the host); kmax[candidate] = its max
-// |symbol|.  The walk is region.hip's block_scale_k: (row, column, channel) of a thread's element advance by the fixed
-// steps (dpi, dpj, dc) of the launch's stride, worked out on the host, with at most one carry each.
-template <bool VEC>
-__global__ void __launch_bounds__(MB_THREADS) block_gain_symbolize_k(const float* __restrict__ y, const float* __restrict__ g,
-                                                                     int R, const unsigned char* __restrict__ rank,
-                                                                     const float* __restrict__ mu,
-                                                                     const int* __restrict__ img, int Hm, int Wm, int C,
-                                                                     int shift, int nbh, int nbw, FastDiv by_c, FastDiv by_w,
-                                                                     int dc, int dpj, int dpi, int* __restrict__ sym,
-                                                                     int* __restrict__ kmax) {
-  constexpr int W = VEC ? 4 : 1;
-  const uint32_t len = (uint32_t)Hm * Wm * C;
-  const float* ys = y + (long long)img[blockIdx.y] * len;
-  const float* ms = mu + (long long)blockIdx.y * len;
-  int* ss = sym + (long long)blockIdx.y * len;
-  const unsigned char* ids = rank + (long long)blockIdx.y * nbh * nbw;
-  const uint32_t tid = blockIdx.x * blockDim.x + threadIdx.x;
-  const uint32_t stride = gridDim.x * blockDim.x;
-  const uint32_t p0 = fdiv(tid * W, by_c);
-  int c = (int)(tid * W - p0 * C), pi = (int)fdiv(p0, by_w);
-  int pj = (int)(p0 - (uint32_t)pi * Wm);
-  const uint32_t n = len / W;   // VEC: C % 4 == 0, so len % 4 == 0
-  int m = 0;
-  for (uint32_t i = tid; i < n; i += stride) {
-    const int row = min((int)ids[(pi >> shift) * nbw + (pj >> shift)], R - 1);
-    const float* gs = g + (long long)row * C + c;
-    if (VEC) {
-      const floatx4v a = reinterpret_cast<const floatx4v*>(ys)[i];
-      const floatx4v b = *reinterpret_cast<const floatx4v*>(gs);
-      const floatx4v u = reinterpret_cast<const floatx4v*>(ms)[i];
-      intx4v k;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        k[j] = symbol_of(sub_rn(mul_rn(a[j], b[j]), u[j]));
-        m = max(m, k[j] < 0 ? -k[j] : k[j]);
-      }
-      reinterpret_cast<intx4v*>(ss)[i] = k;
-    } else {
-      const int k = symbol_of(sub_rn(mul_rn(ys[i], gs[0]), ms[i]));
-      ss[i] = k;
-      m = max(m, k < 0 ? -k : k);
-    }
+// One image is Hm * Wm * C elements (< 2^31: checked on the host).  The walk is region.hip's block_scale_k: (row, column,
+// channel) of a thread's element advance by the fixed steps (dpi, dpj, dc) of the launch's stride, worked out on the
+// host, with at most one carry each.
+struct BlockGainSrc {
+  const float *y, *g, *mu;
+  const unsigned char* rank;
+  const int* img;
+  int R, Wm, C, shift, nbw, nblk;   // nblk: the blocks of one candidate's map
+  FastDiv by_c, by_w;
+  int dc, dpj, dpi;
+  int c, pj, pi;
+  __device__ __forceinline__ void bind(unsigned seg, long long len, long long first, long long) {
+    y += (long long)img[seg] * len;
+    mu += (long long)seg * len;
+    rank += (long long)seg * nblk;
+    const uint32_t p0 = fdiv((uint32_t)first, by_c);
+    c = (int)((uint32_t)first - p0 * C), pi = (int)fdiv(p0, by_w);
+    pj = (int)(p0 - (uint32_t)pi * Wm);
+  }
+  template <class V>
+  __device__ __forceinline__ V at(long long i) const {
+    const int row = min((int)rank[(pi >> shift) * nbw + (pj >> shift)], R - 1);
+    return sub_rn(mul_rn(load_as<V>(y, i), load_as<V>(g + (long long)row * C + c, 0)), load_as<V>(mu, i));
+  }
+  __device__ __forceinline__ void next() {
     c += dc;
     if (c >= C) {
       c -= C;
@@ -152,11 +116,7 @@ __global__ void __launch_bounds__(MB_THREADS) block_gain_symbolize_k(const float
     }
     pi += dpi;
   }
-  m = block_max(m);
-  if (threadIdx.x == 0) atomicMax(kmax + blockIdx.y, m);
-}
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+};
 
 int map_extent(int v, int shift) { return (int)(((long long)v + (1 << shift) - 1) >> shift); }
 
@@ -197,35 +157,15 @@ int ic_block_gain_symbolize_seg(const float* y, int N, int Hm, int Wm, int C, co
   if ((long long)Hm * Wm > 0x7fffffffll / C) return IC_ERR_ARG;   // one image's elements are indexed in 32 bits
   for (int m = 0; m < nseg; ++m)
     if (img[m] < 0 || img[m] >= N) return IC_ERR_ARG;
-  hipStream_t st = (hipStream_t)stream;
-  // the host array is consumed before this returns (a copy from pageable memory is staged by the runtime)
-  hipError_t e = hipMemcpyAsync(img_dev, img, sizeof(int) * nseg, hipMemcpyHostToDevice, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipMemsetAsync(kmax_dev, 0, sizeof(int) * nseg, st);
-  if (e != hipSuccess) return (int)e;
   const bool vec = C % 4 == 0 && aligned16(y) && aligned16(g) && aligned16(mu) && aligned16(sym);
-  const int w = vec ? 4 : 1;
-  const long long work = (long long)Hm * Wm * C / w;
-  const dim3 grid((unsigned)std::min<long long>((work + MB_THREADS - 1) / MB_THREADS, MB_MAXBLOCKS), (unsigned)nseg);
+  const long long len = (long long)Hm * Wm * C;
   const int nbh = map_extent(Hm, shift), nbw = map_extent(Wm, shift);
   // the steps of one grid stride in (row, column, channel)
-  const long long se = (long long)grid.x * MB_THREADS * w, dp = se / C;
+  const long long se = (long long)seg_blocks(len, vec) * SEG_THREADS * (vec ? 4 : 1), dp = se / C;
   const int dc = (int)(se % C), dpj = (int)(dp % Wm), dpi = (int)(dp / Wm);
-  const FastDiv by_c = make_fastdiv((uint32_t)C), by_w = make_fastdiv((uint32_t)Wm);
-  if (vec)
-    hipLaunchKernelGGL(block_gain_symbolize_k<true>, grid, dim3(MB_THREADS), 0, st, y, g, R, rank, mu, img_dev, Hm, Wm, C,
-                       shift, nbh, nbw, by_c, by_w, dc, dpj, dpi, sym, kmax_dev);
-  else
-    hipLaunchKernelGGL(block_gain_symbolize_k<false>, grid, dim3(MB_THREADS), 0, st, y, g, R, rank, mu, img_dev, Hm, Wm, C,
-                       shift, nbh, nbw, by_c, by_w, dc, dpj, dpi, sym, kmax_dev);
-  IC_CHECK_LAUNCH();
-  e = hipMemcpyAsync(kmax_host, kmax_dev, sizeof(int) * nseg, hipMemcpyDeviceToHost, st);
-  if (e != hipSuccess) return (int)e;
-  e = hipStreamSynchronize(st);
-  if (e != hipSuccess) return (int)e;
-  for (int m = 0; m < nseg; ++m)
-    if (kmax_host[m] > IC_CODEC_KMAX) return IC_ERR_ARG;
-  return IC_OK;
+  const BlockGainSrc src{y, g, mu, rank, img_dev, R, Wm, C, shift, nbw, nbh * nbw, make_fastdiv((uint32_t)C),
+                         make_fastdiv((uint32_t)Wm), dc, dpj, dpi, 0, 0, 0};
+  return seg_symbolize(src, vec, nseg, len, img, img_dev, sym, kmax_dev, kmax_host, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -13,6 +13,7 @@
 
 #include "bits_term.h"
 #include "common.h"
+#include "fp_rn.h"
 #include "../../include/imgcomp.h"
 
 namespace {
@@ -145,8 +146,8 @@ __global__ void __launch_bounds__(RM_THREADS) block_sse_k(const float* __restric
       }
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float d = __fsub_rn(va[k], vb[k]);
-        if (k < q.cnt) s[0] = __fadd_rn(s[0], __fmul_rn(d, d));   // never contracted: one rounding each
+        const float d = sub_rn(va[k], vb[k]);
+        if (k < q.cnt) s[0] = fmaf(d, d, s[0]);   // the difference rounded once, the square fused with the sum
       }
     }
     block_sum<1>(s, lds);

@@ -1042,6 +1042,33 @@ std::tuple<Tensor, std::vector<int64_t>> symbolize(const char* ns, const char* w
   return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
 }
 
+// The shared tail of the symbolizers that take a list of candidates (gain_symbolize_seg, requant_seg,
+// block_gain_symbolize_seg): img names, for every `item` ("candidate", "target"), one of the N `source`s ("image",
+// "source") of y; mu holds the items' means back to back and gives the symbols their size.  call(img, img_dev, sym,
+// kmax_dev, kmax_host) makes the C call; an item over the coder's limit is a ValueError under the namespace `ns`.
+template <class Call>
+std::tuple<Tensor, std::vector<int64_t>> symbolize_candidates(const char* ns, const char* what, const char* item,
+                                                              const char* source, const Tensor& y, const Tensor& mu,
+                                                              at::IntArrayRef img, Call call) {
+  const int64_t M = (int64_t)img.size(), N = y.size(0);
+  std::vector<int> im;
+  for (int64_t m = 0; m < M; ++m) {
+    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, ns, ": ", item, " ", m, " names ", source, " ", img[m], " of ", N);
+    im.push_back((int)img[m]);
+  }
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
+  Tensor sym = symbols_out(mu);
+  Tensor kd = at::empty({2 * M}, y.options().dtype(at::kInt));   // the maxima, then img on the device
+  std::vector<int> kmax((size_t)M, 0);
+  const int rc = call(im.data(), kd.data_ptr<int>() + M, sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data());
+  if (rc == IC_ERR_ARG)
+    for (int64_t m = 0; m < M; ++m)
+      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, ns, ": ", item, " ", m, " (", source, " ", img[m],
+                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
+  check_rc(rc, what);
+  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+}
+
 std::tuple<Tensor, int64_t> codec_symbolize(const Tensor& x) {
   check_dense(x, "x");
   TORCH_CHECK(x.numel() > 0, "imgcomp_codec: empty tensor");
@@ -1915,24 +1942,12 @@ std::tuple<Tensor, std::vector<int64_t>> rate_gain_symbolize_seg(const Tensor& y
   TORCH_CHECK(y.device() == g.device() && y.device() == mu.device(), "imgcomp_rate: y, g and mu must be on one device");
   const int64_t M = (int64_t)img.size(), N = y.size(0), C = y.size(-1);
   TORCH_CHECK(N <= 65535 && C <= INT_MAX, "imgcomp_rate: y is too large: ", y.sizes());
-  std::vector<int> im;
-  for (int64_t m = 0; m < M; ++m) {
-    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_rate: candidate ", m, " names image ", img[m], " of ", N);
-    im.push_back((int)img[m]);
-  }
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
-  Tensor sym = symbols_out(mu);
-  Tensor kd = at::empty({2 * M}, y.options().dtype(at::kInt));   // the maxima, then the images
-  std::vector<int> kmax((size_t)M, 0);
-  const int rc = ic_gain_symbolize_seg(y.data_ptr<float>(), N, y.numel() / N / C, (int)C, g.data_ptr<float>(),
-                                       mu.data_ptr<float>(), (int)M, im.data(), kd.data_ptr<int>() + M, sym.data_ptr<int>(),
-                                       kd.data_ptr<int>(), kmax.data(), stream_of(y));
-  if (rc == IC_ERR_ARG)
-    for (int64_t m = 0; m < M; ++m)
-      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_rate: candidate ", m, " (image ", img[m],
-                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "gain_symbolize_seg");
-  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+  return symbolize_candidates("imgcomp_rate", "gain_symbolize_seg", "candidate", "image", y, mu, img,
+                              [&](const int* im, int* img_dev, int* sym, int* kmax_dev, int* kmax_host) {
+                                return ic_gain_symbolize_seg(y.data_ptr<float>(), N, y.numel() / N / C, (int)C,
+                                                             g.data_ptr<float>(), mu.data_ptr<float>(), (int)M, im, img_dev,
+                                                             sym, kmax_dev, kmax_host, stream_of(y));
+                              });
 }
 
 Tensor rate_measure_seg_meta(const Tensor& sym, int64_t nseg, const std::optional<Tensor>&, int64_t, const Tensor&, int64_t,
@@ -1975,24 +1990,13 @@ std::tuple<Tensor, std::vector<int64_t>> transcode_requant_seg(const Tensor& r, 
   }
   const int64_t M = (int64_t)img.size(), N = r.size(0), C = r.size(-1);
   TORCH_CHECK(N <= 65535 && C <= INT_MAX, "imgcomp_transcode: r is too large: ", r.sizes());
-  std::vector<int> im;
-  for (int64_t m = 0; m < M; ++m) {
-    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_transcode: target ", m, " names source ", img[m], " of ", N);
-    im.push_back((int)img[m]);
-  }
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(r.device());
-  Tensor sym = symbols_out(mu2);
-  Tensor kd = at::empty({2 * M}, r.options().dtype(at::kInt));   // the maxima, then the sources
-  std::vector<int> kmax((size_t)M, 0);
-  const int rc = ic_requant_seg(r.data_ptr<float>(), mu1.data_ptr<float>(), N, r.numel() / N / C, (int)C,
-                                a.data_ptr<float>(), b.data_ptr<float>(), mu2.data_ptr<float>(), (int)M, im.data(),
-                                kd.data_ptr<int>() + M, sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(r));
-  if (rc == IC_ERR_ARG)
-    for (int64_t m = 0; m < M; ++m)
-      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_transcode: target ", m, " (source ", img[m],
-                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "requant_seg");
-  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+  return symbolize_candidates("imgcomp_transcode", "requant_seg", "target", "source", r, mu2, img,
+                              [&](const int* im, int* img_dev, int* sym, int* kmax_dev, int* kmax_host) {
+                                return ic_requant_seg(r.data_ptr<float>(), mu1.data_ptr<float>(), N, r.numel() / N / C,
+                                                      (int)C, a.data_ptr<float>(), b.data_ptr<float>(),
+                                                      mu2.data_ptr<float>(), (int)M, im, img_dev, sym, kmax_dev, kmax_host,
+                                                      stream_of(r));
+                              });
 }
 
 std::tuple<Tensor, std::vector<int64_t>> transcode_requant_seg_meta(const Tensor& r, const Tensor& mu1, const Tensor& a,
@@ -2096,25 +2100,14 @@ std::tuple<Tensor, std::vector<int64_t>> alloc_block_gain_symbolize_seg(const Te
               "imgcomp_alloc: y, g, the rank map and mu must be on one device");
   const int64_t M = (int64_t)img.size(), N = y.size(0);
   TORCH_CHECK(N <= 65535 && y.numel() / N <= INT_MAX, "imgcomp_alloc: y is too large: ", y.sizes());
-  std::vector<int> im;
-  for (int64_t m = 0; m < M; ++m) {
-    TORCH_CHECK_VALUE(img[m] >= 0 && img[m] < N, "imgcomp_alloc: candidate ", m, " names image ", img[m], " of ", N);
-    im.push_back((int)img[m]);
-  }
-  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(y.device());
-  Tensor sym = symbols_out(mu);
-  Tensor kd = at::empty({2 * M}, y.options().dtype(at::kInt));   // the maxima, then the images
-  std::vector<int> kmax((size_t)M, 0);
-  const int rc = ic_block_gain_symbolize_seg(y.data_ptr<float>(), (int)N, (int)y.size(1), (int)y.size(2), (int)y.size(3),
-                                             g.data_ptr<float>(), (int)g.size(0), rank.data_ptr<uint8_t>(), (int)shift,
-                                             mu.data_ptr<float>(), (int)M, im.data(), kd.data_ptr<int>() + M,
-                                             sym.data_ptr<int>(), kd.data_ptr<int>(), kmax.data(), stream_of(y));
-  if (rc == IC_ERR_ARG)
-    for (int64_t m = 0; m < M; ++m)
-      TORCH_CHECK_VALUE(kmax[m] <= IC_CODEC_KMAX, "imgcomp_alloc: candidate ", m, " (image ", img[m],
-                        ") has a symbol of magnitude ", kmax[m], ", which exceeds the coder's limit of ", IC_CODEC_KMAX);
-  check_rc(rc, "block_gain_symbolize_seg");
-  return {sym, std::vector<int64_t>(kmax.begin(), kmax.end())};
+  return symbolize_candidates("imgcomp_alloc", "block_gain_symbolize_seg", "candidate", "image", y, mu, img,
+                              [&](const int* im, int* img_dev, int* sym, int* kmax_dev, int* kmax_host) {
+                                return ic_block_gain_symbolize_seg(y.data_ptr<float>(), (int)N, (int)y.size(1),
+                                                                   (int)y.size(2), (int)y.size(3), g.data_ptr<float>(),
+                                                                   (int)g.size(0), rank.data_ptr<uint8_t>(), (int)shift,
+                                                                   mu.data_ptr<float>(), (int)M, im, img_dev, sym, kmax_dev,
+                                                                   kmax_host, stream_of(y));
+                              });
 }
 
 std::tuple<Tensor, std::vector<int64_t>> alloc_block_gain_symbolize_seg_meta(const Tensor& y, const Tensor& g,

@@ -615,8 +615,8 @@ int ic_context_fwd(const float* y_in, const float* mu_h, const float* sigma_h, c
 
 /* ---- gain units (additive to version 4; GainedMeanScaleCompressor2018).  The gain-vector rule: for a table t
  *      (S, C), S >= 2, and a quality q in [0, S-1] held as fp32: s = min((int)floorf(q), S-2), f = q - s,
- *      a = (1-f) t[s][c] + f t[s+1][c] with both products and the sum rounded once each, g[c] = 1.0f where a == 0
- *      and expf(a) elsewhere.  `q` is a host array.  IC_ERR_ARG before any launch for a null pointer, S < 2, C or
+ *      a = fma(f, t[s+1][c], fl((1-f) t[s][c])): 1-f and the lower level's product rounded once each, the upper
+ *      level's product fused with the sum and rounded once; g[c] = 1.0f where a == 0 and expf(a) elsewhere.  `q` is a host array.  IC_ERR_ARG before any launch for a null pointer, S < 2, C or
  *      nq < 1, or a quality that is NaN or outside [0, S-1].  None of them allocates or waits for its stream. ---- */
 /* out[k][c] = the gain of channel c at quality q[k]: (nq, C) */
 int ic_gain_vector(const float* table, int S, int C, const float* q, int nq, float* out, void* stream);
@@ -677,8 +677,9 @@ int ic_block_mse_bwd(const float* a, const float* b, const float* w, int R, cons
  * ic_ce_loss_fwd; with `add` (the shape of out; NULL for none) out = add + that sum, one fp32 addition */
 int ic_block_bits(const float* p, int N, int C, int Hm, int Wm, long long sn, long long sc, long long sh, long long sw,
                   int shift, const float* add, float* out, void* stream);
-/* out[n,bi,bj] = the sum over the block and all channels of (a - b)^2, every operation rounded once; a is walked
- * along its storage, b at its own strides (an, ...) / (bn, ...) */
+/* out[n,bi,bj] = the sum over the block and all channels of (a - b)^2: d = a - b rounded once, s = fma(d, d, s) (the
+ * square fused with the accumulation, rounded once); a is walked along its storage, b at its own strides (an, ...) /
+ * (bn, ...) */
 int ic_block_sse(const float* a, const float* b, int N, int C, int H, int W, long long an, long long ac, long long ah,
                  long long aw, long long bn, long long bc, long long bh, long long bw, int shift, float* out,
                  void* stream);

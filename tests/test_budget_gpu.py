@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from conftest import assert_close
+from planted_ties import _fusable
 from test_budget import search
 from test_codec import draw, random_tables, ref_encode
 from test_gained_gpu import R_MODEL, S, TABLES, _dev, _model, _table_values, _tables
@@ -117,6 +118,29 @@ def test_gain_symbolize_is_scale_then_symbolize_bitwise(C, P, offset):
     assert np.array_equal(sym.cpu().numpy(), want.reshape(-1)), "not numpy on the same fp32 inputs"
     sym2, kmax2 = _lib.rate_ops().gain_symbolize_seg(yd, gd, md, list(IMG))
     assert torch.equal(sym2, sym) and list(kmax2) == list(kmax)
+
+
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "offset1"])
+def test_gain_symbolize_never_fuses_the_product_with_the_difference(offset):
+    """Every element of candidate 0 is planted so that a kernel which contracts the product with the difference into
+    one FMA gives another symbol (`_fusable`): gains of 1.3 and 0.7, whose products are inexact, where the ties of the
+    test above sit behind gains of 1 and 2."""
+    from image_compression_amd import _lib
+    N, M, P, C = 1, 2, 16, 8
+    g = np.empty((M, C), np.float32)
+    g[:, 0::2], g[:, 1::2] = 1.3, 0.7
+    y, mu = np.empty((N, P, C), np.float32), np.empty((M, P, C), np.float32)
+    for c in range(C):
+        y[0, :, c], mu[0, :, c] = _fusable(g[0, c], P, 10 * c + offset)
+    mu[1] = mu[0] + np.float32(0.25)
+    d = y[[0, 0]] * g[:, None, :] - mu
+    assert d.dtype == np.float32 and (np.abs(d[0] - np.trunc(d[0])) == 0.5).all(), "the planted ties are not ties"
+    want = np.rint(d).astype(np.int32)
+    sym, _ = _lib.rate_ops().gain_symbolize_seg(*(_dev(t, offset) for t in (y, g, mu)), [0, 0])
+    got = sym.cpu().numpy().reshape(M, P, C)
+    print(f"gain_symbolize offset {offset}: {int((got != want).sum())} of {want.size} symbols differ from numpy, "
+          f"{int((got[0] != want[0]).sum())} of {want[0].size} planted")
+    assert np.array_equal(got, want), f"{int((got != want).sum())} of {want.size} symbols moved: the product was fused"
 
 
 def test_gain_symbolize_wrapper_and_the_limit():

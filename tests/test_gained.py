@@ -5,6 +5,7 @@ kernels' C entry points and the shape kernels of torch.ops.imgcomp_gain."""
 import ctypes
 import functools
 import struct
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -14,18 +15,39 @@ ARCH = "GainedMeanScaleCompressor2018"
 GAIN_KEYS = {"gain.log_y", "gain.log_inv_y", "gain.log_z", "gain.log_inv_z"}
 
 
-def gain_rule(table, q, dtype=np.float32):
-    """The gain-vector rule of codec.py for one quality: table (S, C) -> g (C,).  In float32 every numpy operation
-    below rounds once, as the kernel's __fmul_rn / __fadd_rn do; in float64 it is the rule's exact statement on the
-    same float32 table and quality."""
+def _fma32(a, b, c):
+    """fl32(a b + c) of float32 operands, rounded once: the exact rational, then the nearest float32 (ties to even)
+    among the float64 rounding's float32 neighbours (a float64 sum rounded again could land on the wrong side)."""
+    exact = Fraction(float(a)) * Fraction(float(b)) + Fraction(float(c))
+    near = np.float32(float(exact))
+    cands = (np.nextafter(near, np.float32(-np.inf)), near, np.nextafter(near, np.float32(np.inf)))
+    return min(cands, key=lambda v: (abs(Fraction(float(v)) - exact), int(v.view(np.uint32)) & 1))
+
+
+def gain_exponent(table, q, dtype=np.float32):
+    """a of the gain-vector rule of codec.py for one quality: table (S, C) -> a (C,).  In float32 it is the rule bit
+    for bit: f and 1 - f one subtraction each, the lower level's product (1 - f) t[s] rounded once, and the upper
+    level's product fused with the sum, a = fma(f, t[s+1], fl((1 - f) t[s])); in float64 it is the rule's exact
+    statement on the same float32 table and quality."""
     t = np.asarray(table, dtype=np.float32).astype(dtype)
     S = t.shape[0]
     q = np.float32(q)
     assert S >= 2 and 0.0 <= q <= S - 1
     s = min(int(np.floor(q)), S - 2)
     f = dtype(q) - dtype(s)
-    a = (dtype(1.0) - f) * t[s] + f * t[s + 1]
-    assert a.dtype == dtype
+    low = (dtype(1.0) - f) * t[s]
+    if dtype is np.float32:
+        a = np.array([_fma32(f, hi, lo) for hi, lo in zip(t[s + 1], low)], dtype=np.float32)
+    else:
+        a = low + f * t[s + 1]
+    assert a.dtype == dtype and a.shape == t[s].shape
+    return a
+
+
+def gain_rule(table, q, dtype=np.float32):
+    """The gain-vector rule of codec.py for one quality: table (S, C) -> g (C,), 1 where a == 0 and exp(a) elsewhere
+    (`gain_exponent`; numpy's exp, not the kernel's expf)."""
+    a = gain_exponent(table, q, dtype)
     return np.where(a == 0, dtype(1.0), np.exp(a))
 
 

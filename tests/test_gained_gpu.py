@@ -11,7 +11,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import HipReluMasks, assert_close, check_relu_ties, rel_err
-from test_gained import cfg_of, gain_rule
+from test_gained import cfg_of, gain_exponent, gain_rule
 from test_mean_scale_gpu import KINDS, TRAIN_SHAPES, _batch, _changed, _ideal_bits, _pad, _spy_prior, _train_inputs
 
 pytestmark = pytest.mark.gpu
@@ -102,6 +102,13 @@ def _table(C, seed=0):
     return np.random.default_rng(seed).uniform(-0.5, 0.5, (S, C)).astype(np.float32)
 
 
+def _alone(a):
+    """A two-level table whose level 0 is a and whose level 1 is zero, on the device."""
+    alone = np.zeros((2, len(a)), np.float32)
+    alone[0] = a
+    return torch.from_numpy(alone).to(DEV)
+
+
 def _ulps(got, want64):
     want64 = np.asarray(want64, dtype=np.float64)
     return float(np.max(np.abs(got.astype(np.float64) - want64) / np.spacing(want64.astype(np.float32))))
@@ -123,7 +130,7 @@ def test_gain_vector_follows_the_rule(C):
         got = ops.gain_vector(td, [float(s)])
         assert torch.equal(got, want), f"level {s} is not expf(t[{s}])"
         assert _ulps(got.cpu().numpy()[0], np.exp(t[s].astype(np.float64))) <= 2.0
-    worst = 0.0
+    worst, apart = 0.0, 0
     qs = [0.5, 1.37, 2.5, 3.999, 4.25, float(np.float32(4.9999))]
     for q in qs:
         got = ops.gain_vector(td, [q]).cpu().numpy()[0]
@@ -131,6 +138,20 @@ def test_gain_vector_follows_the_rule(C):
         worst = max(worst, u)
         assert u <= 4.0, (q, u)
         assert _ulps(got, gain_rule(t, q).astype(np.float64)) <= 2.0      # and the fp32 statement but for expf
+        # the fp32 statement bit for bit, with the kernel's own expf: the rule's exponent a as level 0 of a two-level
+        # table at q = 0, where the kernel forms fma(0, 0, fl(1 a)) = a
+        a = gain_exponent(t, q)
+        want = _bits(ops.gain_vector(_alone(a), [0.0]))[0]
+        moved = int((_bits(got) != want).sum())
+        # the rule this one replaced, two rounded products and a rounded sum: the test tells the two apart
+        two = (np.float32(1.0) - (np.float32(q) - np.float32(int(q)))) * t[int(q)] + \
+            (np.float32(q) - np.float32(int(q))) * t[int(q) + 1]
+        assert two.dtype == np.float32
+        apart += int((_bits(ops.gain_vector(_alone(two), [0.0]))[0] != want).sum())
+        print(f"gain_vector C {C} q {q}: {moved} of {C} gains differ from the rule's bits")
+        assert moved == 0, (q, moved)
+    # (a handful of channels may give no such gain: 5 of them differ in one or two exponents, which expf can merge)
+    assert apart > 0 or C < 64, "no quality here separates the fused rule from two rounded products"
     print(f"gain_vector C {C}: worst distance from the fp64 rule {worst:.2f} ulp")
     # many qualities in one call, past the 64 one launch takes: row k is the single call's
     many = [float(np.float32(v)) for v in np.random.default_rng(1).uniform(0, S - 1, 130)] + [0.0, float(S - 1)]
