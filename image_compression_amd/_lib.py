@@ -225,6 +225,10 @@ SIGNATURES = {
     "ic_context_ws": (c_size, [c_int]),
     "ic_context_fwd": (c_int, [c_void, c_void, c_void, c_void, c_void, c_void, c_void, c_int, c_int, c_int, c_int,
                                     c_void, c_void, c_void, c_size, c_int, c_void]),
+    # h_s as batch-invariant layers: one transposed conv with its epilogue per launch (additive to ic_version 4)
+    "ic_hs_ws": (c_size, [c_int, c_int, c_int, c_int, c_int]),
+    "ic_hs_layer": (c_int, [c_void, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void, c_void, c_int, c_void,
+                            c_void, c_void, c_int, c_void, c_float, c_float, c_void, c_size, c_int, c_void]),
     # gain units: gain vectors from the level tables, the scaling of a latent by them (additive to ic_version 4)
     "ic_gain_vector": (c_int, [c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
     "ic_gain_vector_bwd": (c_int, [c_void, c_void, c_int, c_int, P(c_float), c_int, c_void, c_void]),
@@ -306,6 +310,7 @@ window_ops = _namespace("imgcomp_window", "the decoder of a latent window and th
 transcode_ops = _namespace("imgcomp_transcode", "y's symbols at other qualities from a stream's decoded integers")
 alloc_ops = _namespace("imgcomp_alloc", "the per-block level choice and y's symbols under a level map")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
+hs_ops = _namespace("imgcomp_hs", "h_s as batch-invariant layers, each one launch")
 
 
 def ops():

@@ -99,6 +99,23 @@ for bit: 1 -- the two context convs through the conv plans, in the model's COMPU
 csrc/ckbd_context.hip).  The layout is the same; a model reads only the version it writes, and refuses the other by the
 format-version error before any launch.
 
+The route of h_s (every container)
+----------------------------------
+(sigma, mu) = h_s(z_hat) selects the table row of every symbol of y, so the decoder must repeat h_s bit for bit.  Every
+container's format version says which route computed it, and a model reads only the version it writes:
+    MODEL.HYPER_SYNTHESIS.KERNEL "conv" (default): the transposed convs through the conv plans, in the model's
+        COMPUTE_DTYPE; a per-image path runs them one image at a time.  Version 1 ("ICRC": 1 or 2, by the context).
+    MODEL.HYPER_SYNTHESIS.KERNEL "invariant": one launch per layer of csrc/hs_invariant.hip, once for all images of a
+        call.  Version 2 (INVARIANT_FORMAT_VERSION; "ICRC": 3 or 4, by the context).  The layouts are the same.
+The decodability contract's clause for "invariant": every layer output is one chain of fp32 fmaf (exact products, fp32
+accumulation, fp32 MFMA) that starts from the bias and adds, in this order, the live taps (ky, kx) of the output's phase
+(i % s, j % s) ascending; inside a tap the channel groups of 8 ascending; inside a group the channels +0, +4, +1, +5,
++2, +6, +3, +7; a tap outside the map and a channel past Cin add a product with +0.0.  The order is a function of
+(k, s, Cin) only -- not of N, H, W, the image's index or the position's place in the map -- K is never split and there
+are no atomics.  ReLU is x > 0 ? x : (x != x ? x : 0); sigma = fminf(fmaxf(expf(v), 1e-10), 1e10).  Every pack_* /
+parse_* pair takes `version=` (default: the "conv" number; pack_checkerboard / parse_checkerboard keep `version` for
+the context's route and take `invariant=` beside it).
+
 Per-image checkerboard container (little endian), one image = one bytes object (`compress_each` of a "fused" model)
 --------------------------------------------------------------------------------------------------------------------
 The image is padded as for "ICRP" and its padded form coded as a checkerboard batch of one: h_s on this image alone,
@@ -292,6 +309,7 @@ import numpy as np
 
 MAGIC = b"ICRA"
 FORMAT_VERSION = 1
+INVARIANT_FORMAT_VERSION = 2   # h_s by the batch-invariant kernel: every container but "ICRC" (3 and 4 there)
 KMAX_LIMIT = 2047          # IC_CODEC_KMAX: 2K+1 <= 4095 counts of >= 1 inside a 16-bit total
 MAX_SCALES = 256           # IC_CODEC_MAXL: rows are uint8
 MAX_STEPS = 65536          # IC_CODEC_MAXR
@@ -311,6 +329,8 @@ _IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II")   # the ICRA header's fields,
 CKBD_MAGIC = b"ICRC"
 CKBD_FORMAT_VERSION = 1          # the context from the two convs
 CKBD_FUSED_FORMAT_VERSION = 2    # the context from the fused, batch-invariant kernel
+CKBD_INVARIANT_FORMAT_VERSION = 3         # the two above with h_s by the batch-invariant kernel
+CKBD_FUSED_INVARIANT_FORMAT_VERSION = 4
 _CKBD_HEAD = struct.Struct(_FIELDS + "III")   # the ICRA header's fields with three chunk counts: z, y anchors, y non-anchors
 CKBD_IMAGE_MAGIC = b"ICRK"
 CKBD_IMAGE_FORMAT_VERSION = 1
@@ -479,6 +499,14 @@ def _fixed_bytes(head, h, y_symbols=_whole_y, var=0):
     return head.size + var + 4 * nc + CHUNK_HEAD * nc
 
 
+def _route_version(version, conv):
+    """`version` of a container whose conv-route number is `conv`: that, or INVARIANT_FORMAT_VERSION."""
+    if version not in (conv, INVARIANT_FORMAT_VERSION):
+        raise ValueError(f"codec: no format version {version} of this container ({conv}: h_s through the conv plans, "
+                         f"{INVARIANT_FORMAT_VERSION}: h_s by the batch-invariant kernel)")
+    return int(version)
+
+
 def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y",), y_symbols=_whole_y, var=b""):
     """One bytes object from the header `h`, which `check` passes, the streams' chunk-length tables and their
     payloads; `extra`: the header fields after the chunk counts; `var`: the bytes of the header's variable-length
@@ -554,16 +582,18 @@ def fixed_bytes(h):
     return _fixed_bytes(_HEAD, h)
 
 
-def pack(h, lens_z, lens_y, payload_z, payload_y):
+def pack(h, lens_z, lens_y, payload_z, payload_y, version=FORMAT_VERSION):
     """One bytes object from the header, the two chunk-length tables and the two payloads."""
-    return _pack(_HEAD, MAGIC, FORMAT_VERSION, _check_header, h, (lens_z, lens_y), (payload_z, payload_y))
+    v = _route_version(version, FORMAT_VERSION)
+    return _pack(_HEAD, MAGIC, v, _check_header, h, (lens_z, lens_y), (payload_z, payload_y))
 
 
-def parse(data, abi, compute_dtype):
+def parse(data, abi, compute_dtype, version=FORMAT_VERSION):
     """(Header, lens_z, lens_y, payload_z, payload_y) of a container made by `pack`; `abi` and
     `compute_dtype` are the running build's ic_version() and the model's arithmetic, which the
     stream must match.  Raises ValueError on anything inconsistent; nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _HEAD, MAGIC, FORMAT_VERSION, Header, _check_header)
+    v = _route_version(version, FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _HEAD, MAGIC, v, Header, _check_header)
 
 
 def _check_image_header(h):
@@ -580,17 +610,18 @@ def image_fixed_bytes(h):
     return _fixed_bytes(_IMAGE_HEAD, h)
 
 
-def pack_image(h, lens_z, lens_y, payload_z, payload_y):
+def pack_image(h, lens_z, lens_y, payload_z, payload_y, version=IMAGE_FORMAT_VERSION):
     """One bytes object for one image from its ImageHeader, chunk-length tables and payloads."""
-    return _pack(_IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, _check_image_header, h, (lens_z, lens_y),
-                 (payload_z, payload_y), (h.height, h.width))
+    v = _route_version(version, IMAGE_FORMAT_VERSION)
+    return _pack(_IMAGE_HEAD, IMAGE_MAGIC, v, _check_image_header, h, (lens_z, lens_y), (payload_z, payload_y),
+                 (h.height, h.width))
 
 
-def parse_image(data, abi, compute_dtype):
+def parse_image(data, abi, compute_dtype, version=IMAGE_FORMAT_VERSION):
     """(ImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_image`: the
     checks of `parse`, and those of the image size.  Nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, IMAGE_FORMAT_VERSION, ImageHeader,
-                  _check_image_header)
+    v = _route_version(version, IMAGE_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _IMAGE_HEAD, IMAGE_MAGIC, v, ImageHeader, _check_image_header)
 
 
 # ---- checkerboard container "ICRC": y in two bitstreams, the anchors and the non-anchors
@@ -634,24 +665,27 @@ def checkerboard_fixed_bytes(h):
     return _fixed_bytes(_CKBD_HEAD, h, _half_symbols)
 
 
-def _checkerboard_version(version):
+def checkerboard_version(version, invariant=False):
+    """The number on the wire: `version` (1 or 2) names the route of the context, `invariant` that of h_s."""
     if version not in (CKBD_FORMAT_VERSION, CKBD_FUSED_FORMAT_VERSION):
         raise ValueError(f"codec: no checkerboard format version {version}")
-    return int(version)
+    return int(version) + (CKBD_INVARIANT_FORMAT_VERSION - CKBD_FORMAT_VERSION if invariant else 0)
 
 
-def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn, version=CKBD_FORMAT_VERSION):
+def pack_checkerboard(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn, version=CKBD_FORMAT_VERSION,
+                      invariant=False):
     """One bytes object from the header, the three chunk-length tables and the three payloads (z, the anchors
-    of y, the non-anchors of y); `version`: 1 -- the context came from the convs, 2 -- from the fused kernel."""
-    return _pack(_CKBD_HEAD, CKBD_MAGIC, _checkerboard_version(version), _check_checkerboard_header, h,
+    of y, the non-anchors of y); `version`: 1 -- the context came from the convs, 2 -- from the fused kernel.
+    `invariant`: h_s ran through the batch-invariant kernel; the container then carries 3 or 4 in their place."""
+    return _pack(_CKBD_HEAD, CKBD_MAGIC, checkerboard_version(version, invariant), _check_checkerboard_header, h,
                  (lens_z, lens_ya, lens_yn), (payload_z, payload_ya, payload_yn), (), _HALVES, _half_symbols)
 
 
-def parse_checkerboard(data, abi, compute_dtype, version=CKBD_FORMAT_VERSION):
+def parse_checkerboard(data, abi, compute_dtype, version=CKBD_FORMAT_VERSION, invariant=False):
     """(Header, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
-    `pack_checkerboard` with this `version`, with the checks of `parse`.  Raises ValueError on anything
-    inconsistent, the other version included; nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, _checkerboard_version(version), Header,
+    `pack_checkerboard` with this `version` and `invariant`, with the checks of `parse`.  Raises ValueError on anything
+    inconsistent, every other version included; nothing is launched here."""
+    return _parse(data, abi, compute_dtype, _CKBD_HEAD, CKBD_MAGIC, checkerboard_version(version, invariant), Header,
                   _check_checkerboard_header, _HALVES, _half_symbols, " (y in two equal halves)")
 
 
@@ -666,18 +700,21 @@ def checkerboard_image_fixed_bytes(h):
     return _fixed_bytes(_CKBD_IMAGE_HEAD, h, _half_symbols)
 
 
-def pack_checkerboard_image(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn):
+def pack_checkerboard_image(h, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn,
+                            version=CKBD_IMAGE_FORMAT_VERSION):
     """One bytes object for one image from its ImageHeader, the three chunk-length tables and the three payloads."""
-    return _pack(_CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, CKBD_IMAGE_FORMAT_VERSION, _check_checkerboard_image_header, h,
+    v = _route_version(version, CKBD_IMAGE_FORMAT_VERSION)
+    return _pack(_CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, v, _check_checkerboard_image_header, h,
                  (lens_z, lens_ya, lens_yn), (payload_z, payload_ya, payload_yn), (h.height, h.width), _HALVES,
                  _half_symbols)
 
 
-def parse_checkerboard_image(data, abi, compute_dtype):
+def parse_checkerboard_image(data, abi, compute_dtype, version=CKBD_IMAGE_FORMAT_VERSION):
     """(ImageHeader, lens_z, lens_ya, lens_yn, payload_z, payload_ya, payload_yn) of a container made by
     `pack_checkerboard_image`: the checks of `parse_checkerboard`, and those of the image size.  Nothing is
     launched here."""
-    return _parse(data, abi, compute_dtype, _CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, CKBD_IMAGE_FORMAT_VERSION, ImageHeader,
+    v = _route_version(version, CKBD_IMAGE_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _CKBD_IMAGE_HEAD, CKBD_IMAGE_MAGIC, v, ImageHeader,
                   _check_checkerboard_image_header, _HALVES, _half_symbols, " (y in two equal halves)")
 
 
@@ -711,30 +748,33 @@ def gained_image_fixed_bytes(h):
     return _fixed_bytes(_GAINED_IMAGE_HEAD, h)
 
 
-def pack_gained(h, lens_z, lens_y, payload_z, payload_y):
+def pack_gained(h, lens_z, lens_y, payload_z, payload_y, version=GAINED_FORMAT_VERSION):
     """One bytes object from a GainedHeader, the two chunk-length tables and the two payloads."""
-    return _pack(_GAINED_HEAD, GAINED_MAGIC, GAINED_FORMAT_VERSION, _check_gained_header, h, (lens_z, lens_y),
-                 (payload_z, payload_y), (h.levels, h.quality))
+    v = _route_version(version, GAINED_FORMAT_VERSION)
+    return _pack(_GAINED_HEAD, GAINED_MAGIC, v, _check_gained_header, h, (lens_z, lens_y), (payload_z, payload_y),
+                 (h.levels, h.quality))
 
 
-def parse_gained(data, abi, compute_dtype):
+def parse_gained(data, abi, compute_dtype, version=GAINED_FORMAT_VERSION):
     """(GainedHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_gained`: the checks of
     `parse`, and those of the levels and the quality.  Nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _GAINED_HEAD, GAINED_MAGIC, GAINED_FORMAT_VERSION, GainedHeader,
-                  _check_gained_header)
+    v = _route_version(version, GAINED_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _GAINED_HEAD, GAINED_MAGIC, v, GainedHeader, _check_gained_header)
 
 
-def pack_gained_image(h, lens_z, lens_y, payload_z, payload_y):
+def pack_gained_image(h, lens_z, lens_y, payload_z, payload_y, version=GAINED_FORMAT_VERSION):
     """One bytes object for one image from its GainedImageHeader, chunk-length tables and payloads."""
-    return _pack(_GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION, _check_gained_image_header, h,
-                 (lens_z, lens_y), (payload_z, payload_y), (h.height, h.width, h.levels, h.quality))
+    v = _route_version(version, GAINED_FORMAT_VERSION)
+    return _pack(_GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, v, _check_gained_image_header, h, (lens_z, lens_y),
+                 (payload_z, payload_y), (h.height, h.width, h.levels, h.quality))
 
 
-def parse_gained_image(data, abi, compute_dtype):
+def parse_gained_image(data, abi, compute_dtype, version=GAINED_FORMAT_VERSION):
     """(GainedImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_gained_image`: the
     checks of `parse_image`, and those of the levels and the quality.  Nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, GAINED_FORMAT_VERSION,
-                  GainedImageHeader, _check_gained_image_header)
+    v = _route_version(version, GAINED_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, v, GainedImageHeader,
+                  _check_gained_image_header)
 
 
 # ---- coding to a byte budget: the search rule of `compress_each_to` (the docstring's last section)
@@ -958,33 +998,36 @@ def region_image_fixed_bytes(h):
     return _fixed_bytes(_REGION_IMAGE_HEAD, h, var=_map_bytes(h))
 
 
-def pack_region(h, lens_z, lens_y, payload_z, payload_y):
+def pack_region(h, lens_z, lens_y, payload_z, payload_y, version=REGION_FORMAT_VERSION):
     """One bytes object from a RegionHeader, the two chunk-length tables and the two payloads."""
     _check_region_header(h)
-    return _pack(_REGION_HEAD, REGION_MAGIC, REGION_FORMAT_VERSION, _check_region_header, h, (lens_z, lens_y),
-                 (payload_z, payload_y), (h.levels, h.map_h, h.map_w), var=_packed_map(h))
+    v = _route_version(version, REGION_FORMAT_VERSION)
+    return _pack(_REGION_HEAD, REGION_MAGIC, v, _check_region_header, h, (lens_z, lens_y), (payload_z, payload_y),
+                 (h.levels, h.map_h, h.map_w), var=_packed_map(h))
 
 
-def parse_region(data, abi, compute_dtype):
+def parse_region(data, abi, compute_dtype, version=REGION_FORMAT_VERSION):
     """(RegionHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_region`: the checks of
     `parse`, and those of the levels and the map.  Nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _REGION_HEAD, REGION_MAGIC, REGION_FORMAT_VERSION, RegionHeader,
-                  _check_region_header, var=(_map_bytes, _take_map(False)))
+    v = _route_version(version, REGION_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _REGION_HEAD, REGION_MAGIC, v, RegionHeader, _check_region_header,
+                  var=(_map_bytes, _take_map(False)))
 
 
-def pack_region_image(h, lens_z, lens_y, payload_z, payload_y):
+def pack_region_image(h, lens_z, lens_y, payload_z, payload_y, version=REGION_FORMAT_VERSION):
     """One bytes object for one image from its RegionImageHeader, chunk-length tables and payloads."""
     _check_region_image_header(h)
-    return _pack(_REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, REGION_FORMAT_VERSION, _check_region_image_header, h,
-                 (lens_z, lens_y), (payload_z, payload_y), (h.height, h.width, h.levels, h.map_h, h.map_w),
-                 var=_packed_map(h))
+    v = _route_version(version, REGION_FORMAT_VERSION)
+    return _pack(_REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, v, _check_region_image_header, h, (lens_z, lens_y),
+                 (payload_z, payload_y), (h.height, h.width, h.levels, h.map_h, h.map_w), var=_packed_map(h))
 
 
-def parse_region_image(data, abi, compute_dtype):
+def parse_region_image(data, abi, compute_dtype, version=REGION_FORMAT_VERSION):
     """(RegionImageHeader, lens_z, lens_y, payload_z, payload_y) of a container made by `pack_region_image`: the
     checks of `parse_image`, and those of the levels and the map.  Nothing is launched here."""
-    return _parse(data, abi, compute_dtype, _REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, REGION_FORMAT_VERSION,
-                  RegionImageHeader, _check_region_image_header, var=(_map_bytes, _take_map(True)))
+    v = _route_version(version, REGION_FORMAT_VERSION)
+    return _parse(data, abi, compute_dtype, _REGION_IMAGE_HEAD, REGION_IMAGE_MAGIC, v, RegionImageHeader,
+                  _check_region_image_header, var=(_map_bytes, _take_map(True)))
 
 
 # ---- decoding a pixel window of a per-image stream: what it reads (the docstring's last section)

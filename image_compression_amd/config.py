@@ -80,6 +80,10 @@ _DEFAULTS = {
         # CheckerboardCompressor2018, inference paths only: "conv" -- the two context convs through the conv plans;
         # "fused" -- one batch-invariant kernel (csrc/ckbd_context.hip), which also gives the model per-image streams
         "CONTEXT": {"KERNEL": "conv"},
+        # every model, inference paths only: "conv" -- h_s through the conv plans, one image at a time where a stream
+        # must decode alone; "invariant" -- h_s by one batch-invariant kernel per layer (csrc/hs_invariant.hip), once
+        # per call for all images.  The two give different sigma bits: streams carry the route in their format version
+        "HYPER_SYNTHESIS": {"KERNEL": "conv"},
     },
     "SOLVER": {"USE_ITER": True, "GD_STEPS": 1, "IMS_PER_BATCH": 2, "NUM_CHECKPOINTS": 10,
                "CHECKPOINTER_NAME": "IterCheckpointer", "TRAINER_NAME": "Trainer", "EVALUATOR_NAME": "",

@@ -1567,6 +1567,110 @@ std::tuple<Tensor, Tensor> ctx_context_fwd_ws_meta(const Tensor& y_in, const Ten
   return ctx_context_fwd_meta(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale);
 }
 
+// ---------------------------------------------------------------- h_s as batch-invariant layers (imgcomp_hs)
+// x: (N, H, W, Cin) dense channels-last storage; w: (Cin, Cout, k, k) and b: (Cout) as ConvTranspose2d holds them.
+// Returns (out, out2), out2 with no element when there is no second head.
+struct HsShape {
+  int64_t N, H, W, Cin, Cout, k, heads;
+};
+
+HsShape check_hs(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride, int64_t epilogue,
+                 const c10::optional<Tensor>& w2, const c10::optional<Tensor>& b2, int64_t epilogue2, bool device) {
+  TORCH_CHECK(x.dim() == 4 && x.is_contiguous() && x.numel() > 0, "imgcomp_hs: x must be a contiguous, non-empty "
+              "(N, H, W, C) tensor, got ", x.sizes());
+  for (int64_t d = 0; d < 4; ++d) TORCH_CHECK(x.size(d) <= INT_MAX / 2, "imgcomp_hs: x is too large: ", x.sizes());
+  TORCH_CHECK(w.dim() == 4 && w.is_contiguous() && w.size(0) == x.size(3) && w.size(2) == w.size(3) && w.size(1) >= 1,
+              "imgcomp_hs: the weight must be a contiguous (", x.size(3), ", Cout, k, k) tensor, got ", w.sizes());
+  HsShape g{x.size(0), x.size(1), x.size(2), x.size(3), w.size(1), w.size(2), 1};
+  TORCH_CHECK(b.dim() == 1 && b.size(0) == g.Cout && b.is_contiguous(), "imgcomp_hs: the bias must be (", g.Cout,
+              "), got ", b.sizes());
+  const bool second = w2.has_value() && w2->defined();
+  TORCH_CHECK(second == (b2.has_value() && b2->defined()), "imgcomp_hs: the second head needs a weight and a bias");
+  if (second) {
+    g.heads = 2;
+    TORCH_CHECK(w2->sizes() == w.sizes() && w2->is_contiguous() && b2->sizes() == b.sizes() && b2->is_contiguous(),
+                "imgcomp_hs: the second head's weight ", w2->sizes(), " and bias ", b2->sizes(),
+                " must be contiguous and shaped as the first's, ", w.sizes(), " and ", b.sizes());
+  }
+  TORCH_CHECK(g.Cin <= INT_MAX && g.Cout <= INT_MAX && g.k <= INT_MAX &&
+                  ic_hs_ws((int)g.Cin, (int)g.Cout, (int)g.k, (int)std::min<int64_t>(std::max<int64_t>(stride, 0), 3),
+                           (int)g.heads) > 0,
+              "imgcomp_hs: no kernel for k ", g.k, ", stride ", stride, ", channels ", g.Cin, " -> ", g.Cout,
+              " (k odd and <= 5, stride 1 or 2, 1 .. ", IC_HS_MAXC, " channels)");
+  for (int64_t e : {epilogue, second ? epilogue2 : (int64_t)IC_HS_NONE})
+    TORCH_CHECK(e == IC_HS_NONE || e == IC_HS_RELU || e == IC_HS_EXP_CLAMP, "imgcomp_hs: no epilogue ", e);
+  if (device) {
+    check_operand(x, "x");
+    for (const Tensor* t : {&w, &b, second ? &*w2 : &w, second ? &*b2 : &b}) {
+      check_operand(*t, "a weight or bias");
+      TORCH_CHECK(t->device() == x.device(), "imgcomp_hs: the weights must be on x's device");
+    }
+  } else {
+    TORCH_CHECK(x.scalar_type() == at::kFloat && w.scalar_type() == at::kFloat && b.scalar_type() == at::kFloat,
+                "imgcomp_hs: operands must be float32");
+  }
+  return g;
+}
+
+std::tuple<Tensor, Tensor> hs_launch(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride, int64_t epilogue,
+                                     const c10::optional<Tensor>& w2, const c10::optional<Tensor>& b2,
+                                     int64_t epilogue2, double lo, double hi, Tensor* own_ws, bool packed) {
+  const HsShape g = check_hs(x, w, b, stride, epilogue, w2, b2, epilogue2, true);
+  const size_t nb = ic_hs_ws((int)g.Cin, (int)g.Cout, (int)g.k, (int)stride, (int)g.heads);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(x.device());
+  Tensor ws;
+  if (own_ws) {
+    TORCH_CHECK(own_ws->is_cuda() && own_ws->scalar_type() == at::kByte && own_ws->is_contiguous() &&
+                    own_ws->device() == x.device(),
+                "imgcomp_hs: ws must be a contiguous uint8 tensor on x's device");
+    if ((size_t)own_ws->numel() < nb) {
+      TORCH_CHECK(!packed, "imgcomp_hs: packed weights expected in a workspace of ", own_ws->numel(),
+                  " bytes, the op needs ", nb);
+      own_ws->resize_({(int64_t)nb});
+    }
+    ws = *own_ws;
+  } else {
+    ws = workspace(x, nb);
+  }
+  Tensor out = at::empty({g.N, stride * g.H, stride * g.W, g.Cout}, x.options());
+  Tensor out2 = g.heads == 2 ? at::empty_like(out) : at::empty({0}, x.options());
+  check_rc(ic_hs_layer(x.data_ptr<float>(), (int)g.N, (int)g.H, (int)g.W, (int)g.Cin, (int)g.Cout, (int)g.k, (int)stride,
+                       w.data_ptr<float>(), b.data_ptr<float>(), (int)epilogue, out.data_ptr<float>(),
+                       g.heads == 2 ? w2->data_ptr<float>() : nullptr, g.heads == 2 ? b2->data_ptr<float>() : nullptr,
+                       g.heads == 2 ? (int)epilogue2 : 0, g.heads == 2 ? out2.data_ptr<float>() : nullptr, (float)lo,
+                       (float)hi, ws.data_ptr(), (size_t)ws.numel(), packed ? 1 : 0, stream_of(x)),
+           "hs layer");
+  return {out, out2};
+}
+
+std::tuple<Tensor, Tensor> hs_layer(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride, int64_t epilogue,
+                                    const c10::optional<Tensor>& w2, const c10::optional<Tensor>& b2, int64_t epilogue2,
+                                    double lo, double hi) {
+  return hs_launch(x, w, b, stride, epilogue, w2, b2, epilogue2, lo, hi, nullptr, false);
+}
+
+// the packed weights kept by the caller: written to `ws` (grown when too small), or with `packed` read from it
+std::tuple<Tensor, Tensor> hs_layer_ws(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride,
+                                       int64_t epilogue, const c10::optional<Tensor>& w2,
+                                       const c10::optional<Tensor>& b2, int64_t epilogue2, double lo, double hi,
+                                       Tensor& ws, bool packed) {
+  return hs_launch(x, w, b, stride, epilogue, w2, b2, epilogue2, lo, hi, &ws, packed);
+}
+
+std::tuple<Tensor, Tensor> hs_layer_meta(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride,
+                                         int64_t epilogue, const c10::optional<Tensor>& w2,
+                                         const c10::optional<Tensor>& b2, int64_t epilogue2, double lo, double hi) {
+  const HsShape g = check_hs(x, w, b, stride, epilogue, w2, b2, epilogue2, false);
+  Tensor out = at::empty({g.N, stride * g.H, stride * g.W, g.Cout}, x.options());
+  return {out, g.heads == 2 ? at::empty_like(out) : at::empty({0}, x.options())};
+}
+std::tuple<Tensor, Tensor> hs_layer_ws_meta(const Tensor& x, const Tensor& w, const Tensor& b, int64_t stride,
+                                            int64_t epilogue, const c10::optional<Tensor>& w2,
+                                            const c10::optional<Tensor>& b2, int64_t epilogue2, double lo, double hi,
+                                            Tensor& ws, bool packed) {
+  return hs_layer_meta(x, w, b, stride, epilogue, w2, b2, epilogue2, lo, hi);
+}
+
 // ---------------------------------------------------------------- gain units (imgcomp_gain)
 // A level table is (S, C); a set of gain vectors (rows, C), one row per quality; a latent is a contiguous
 // (N, *, C) tensor, the channels-last storage the coder flattens, scaled by row 0 (rows == 1) or by row n.
@@ -2684,6 +2788,25 @@ TORCH_LIBRARY_IMPL(imgcomp_ctx, CUDA, m) {
 TORCH_LIBRARY_IMPL(imgcomp_ctx, Meta, m) {
   m.impl("context_fwd", ctx_context_fwd_meta);
   m.impl("context_fwd_ws", ctx_context_fwd_ws_meta);
+}
+
+// h_s as batch-invariant layers (MODEL.HYPER_SYNTHESIS.KERNEL "invariant"): additive, in a namespace of its own.
+// Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_hs, m) {
+  m.def("layer(Tensor x, Tensor w, Tensor b, int stride, int epilogue, Tensor? w2, Tensor? b2, int epilogue2, "
+        "float lo, float hi) -> (Tensor, Tensor)");
+  m.def("layer_ws(Tensor x, Tensor w, Tensor b, int stride, int epilogue, Tensor? w2, Tensor? b2, int epilogue2, "
+        "float lo, float hi, Tensor(a!) ws, bool packed) -> (Tensor, Tensor)");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_hs, CUDA, m) {
+  m.impl("layer", hs_layer);
+  m.impl("layer_ws", hs_layer_ws);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_hs, Meta, m) {
+  m.impl("layer", hs_layer_meta);
+  m.impl("layer_ws", hs_layer_ws_meta);
 }
 
 // The gain units' ops (GainedMeanScaleCompressor2018): additive, in a namespace of their own.

@@ -926,6 +926,56 @@ def ckbd_context(y_in, mu_h, sigma_h, w_mean, b_mean, w_scale, b_scale):
     return _from_last(mu), _from_last(sigma)
 
 
+# ============================================================== h_s as batch-invariant layers
+HS_EPILOGUES = {"none": 0, "relu": 1, "exp_clamp": 2}   # IC_HS_NONE / IC_HS_RELU / IC_HS_EXP_CLAMP (include/imgcomp.h)
+HS_MAX_KERNEL, HS_STRIDES, HS_MAX_CHANNELS = 5, (1, 2), 4096   # what csrc/hs_invariant.hip serves (k odd)
+HS_SIGMA_CLAMP = (1e-10, 1e10)   # h_s's clamp of exp(.) (prior_synthesis.py), the exp_clamp epilogue's default
+
+
+def hs_supported(cin, cout, k, stride):
+    """Whether `hs_layer` serves ConvTranspose2d(cin, cout, k, stride, padding=k // 2, output_padding=stride - 1)."""
+    return (1 <= int(cin) <= HS_MAX_CHANNELS and 1 <= int(cout) <= HS_MAX_CHANNELS and int(k) % 2 == 1
+            and 1 <= int(k) <= HS_MAX_KERNEL and int(stride) in HS_STRIDES)
+
+
+def hs_layer(x, weight, bias, stride, epilogue, second=None, clamp=HS_SIGMA_CLAMP):
+    """One layer of h_s by the batch-invariant kernel (torch.ops.imgcomp_hs.layer, csrc/hs_invariant.hip):
+    `conv_transpose2d(x, weight, bias, stride, padding=k // 2, output_padding=stride - 1)` followed by `epilogue`
+    ("none", "relu", or "exp_clamp": clamp(exp(.), *clamp)), in exact fp32, on the logical (N, C, H, W) view of
+    channels-last storage.  `second` = (weight, bias, epilogue): a second head on the same input in the same launch;
+    the result is then a pair.  Every output's bits depend on the values its taps see, the weights and
+    (k, stride, Cin) only -- not on the batch, the map's size or the position's place in it (the order: codec.py).
+    Inference only: no autograd node.  Inside `weight_cache()` the repacked taps are kept per (weights, versions)."""
+    heads = [(weight, bias, epilogue)] + ([tuple(second)] if second is not None else [])
+    params = [t for w, b, _ in heads for t in (w, b)]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, *params)):
+        raise RuntimeError("hs_layer has no backward: call it under torch.no_grad() (training runs the convs)")
+    for _, _, e in heads:
+        if e not in HS_EPILOGUES:
+            raise ValueError(f"hs_layer: no epilogue {e!r} (one of {sorted(HS_EPILOGUES)})")
+    _lib.require_device(x, *params)
+    xl = _ckbd_last(x)
+    ps = [t.detach().contiguous() for t in params]
+    w2, b2 = (ps[2], ps[3]) if second is not None else (None, None)
+    args = (xl, ps[0], ps[1], int(stride), HS_EPILOGUES[epilogue], w2, b2,
+            HS_EPILOGUES[heads[-1][2]] if second is not None else 0, float(clamp[0]), float(clamp[1]))
+    if _wcache_on(weight):
+        # one entry per first weight; the second head's weight it was packed with is part of its validity
+        e, hit = _wcache_get("hs", weight, (tuple(weight.shape), int(stride), len(heads)))
+        if second is not None:
+            other = e.get("other")
+            hit = hit and other is not None and other[0]() is second[0] and other[1] == second[0]._version
+            e["other"] = (weakref.ref(second[0]), second[0]._version)
+        if "ws" not in e:
+            e["ws"] = torch.empty(16, dtype=torch.uint8, device=xl.device)
+        packed = hit and e.get("packed", False)
+        out, out2 = _lib.hs_ops().layer_ws(*args, e["ws"], bool(packed))
+        e["packed"] = True
+    else:
+        out, out2 = _lib.hs_ops().layer(*args)
+    return _from_last(out) if second is None else (_from_last(out), _from_last(out2))
+
+
 # ============================================================== gain units
 class GainVectorFn(Function):
     """(len(q), C) gain vectors of the level table (S, C) at the qualities q (a tuple of floats in [0, S-1]): the

@@ -5,7 +5,7 @@ import math
 
 import torch.nn as nn
 
-from ...functional import ExpClampFn
+from ...functional import ExpClampFn, hs_layer, hs_supported
 from ..layers import ConvTranspose2d, ReLU
 
 
@@ -25,6 +25,34 @@ class HyperpriorSynthesisTransform(nn.Module):
             if i < n - 1:
                 mods.append(ReLU())
         self._layers = nn.Sequential(*mods)
+        # how the inference paths compute h_s (MODEL.HYPER_SYNTHESIS.KERNEL); no parameter or state-dict key depends on it
+        self.kernel = cfg.MODEL.get("HYPER_SYNTHESIS", {}).get("KERNEL", "conv")
+        if self.kernel not in ("conv", "invariant"):
+            raise ValueError(f'MODEL.HYPER_SYNTHESIS.KERNEL {self.kernel!r}: expected "conv" or "invariant"')
+        if self.kernel == "invariant":
+            for conv in self.convs():
+                k, s = conv.kernel_size[0], conv.stride[0]
+                if not hs_supported(conv.in_channels, conv.out_channels, k, s):
+                    raise ValueError(f'MODEL.HYPER_SYNTHESIS.KERNEL "invariant": no kernel for the h_s layer k {k}, stride '
+                                     f"{s}, channels {conv.in_channels} -> {conv.out_channels} (k odd and at most 5, "
+                                     "stride 1 or 2, 1 .. 4096 channels)")
+
+    def convs(self):
+        """The transposed convs of h_s, in order."""
+        return [m for m in self._layers if isinstance(m, ConvTranspose2d)]
+
+    def invariant(self, z_hat, second=None):
+        """forward(z_hat) by the batch-invariant kernel (functional.hs_layer): one launch per layer, the ReLUs and the
+        exp-clamp in the epilogues.  `second` = (weight, bias) of a second head shaped like the last layer, on the
+        trunk activation and in the last launch: the result is then (sigma, that head's plain output).  Inference
+        only; image n's bits do not depend on the batch."""
+        convs = self.convs()
+        t = z_hat
+        for conv in convs[:-1]:
+            t = hs_layer(t, conv.weight, conv.bias, conv.stride[0], "relu")
+        last = convs[-1]
+        return hs_layer(t, last.weight, last.bias, last.stride[0], "exp_clamp",
+                        second=None if second is None else (*second, "none"), clamp=(1e-10, 1e10))
 
     def forward(self, x):
         return ExpClampFn.apply(self._layers(x), 1e-10, 1e10)

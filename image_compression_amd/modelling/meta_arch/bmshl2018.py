@@ -126,6 +126,14 @@ class Compressor2018(nn.Module):
         # the hyperprior branch (h_a, factorized model, h_s, the y likelihood) on a second
         # stream, concurrent with the synthesis transform (see forward)
         self.concurrent_hyperprior = True
+        # how the inference paths compute h_s: "conv" (the conv plans) or "invariant" (functional.hs_layer); validated
+        # by HyperpriorSynthesisTransform.  It is the streams' format version (`_format_version`)
+        self.hs_kernel = self.prior_synthesis.kernel
+
+    def _hs_invariant(self):
+        """Whether h_s runs through the batch-invariant kernel: MODEL.HYPER_SYNTHESIS.KERNEL "invariant", outside
+        training mode."""
+        return self.hs_kernel == "invariant" and not self.training
 
     def hyperprior_modules(self):
         """The modules whose forward, and so whose backward, run on the hyperprior side stream
@@ -187,7 +195,9 @@ class Compressor2018(nn.Module):
         # forward hook on cm (a caller observing its (q, p)) the call stays whole (serial)
         hooked = bool(cm._forward_hooks or cm._forward_pre_hooks or nn.modules.module._global_forward_hooks
                       or nn.modules.module._global_forward_pre_hooks)
-        if self.concurrent_hyperprior and x.is_cuda and hasattr(cm, "quantize") and not hooked:
+        # under "invariant" the eval forward is the serial step: its sigma comes from `_prior`, as the coder's does
+        if (self.concurrent_hyperprior and x.is_cuda and hasattr(cm, "quantize") and not hooked
+                and not self._hs_invariant()):
             # every tensor that crosses streams passes a _StreamEdge: its gradient, computed on
             # one stream and consumed on the other, is recorded on the consumer's stream, so the
             # caching allocator does not hand its memory to the producer stream's next
@@ -300,6 +310,9 @@ class Compressor2018(nn.Module):
 
     def _prior(self, z_hat):
         """(sigma, mean) from the hyper-latent's integers; mean None: y is coded about 0."""
+        if self._hs_invariant():   # inference only: the eval forward's sigma carries no graph
+            with torch.no_grad():
+                return self.prior_synthesis.invariant(z_hat), None
         return self.prior_synthesis(z_hat), None
 
     def _stream_kind(self):
@@ -317,8 +330,27 @@ class Compressor2018(nn.Module):
         sigma, mean = prior
         return self.conditional_model.decompress(py, sigma, ly, h.kmax_y, h.R, mean=mean)
 
-    _pack, _parse = staticmethod(_codec.pack), staticmethod(_codec.parse)
-    _pack_image, _parse_image = staticmethod(_codec.pack_image), staticmethod(_codec.parse_image)
+    # the model's containers (pack, parse, per-image pack, per-image parse) and the format version it writes and
+    # reads in them: the route that computed h_s, so a stream is only ever decoded by the arithmetic that coded it
+    _containers = (_codec.pack, _codec.parse, _codec.pack_image, _codec.parse_image)
+
+    def _format_version(self):
+        return _codec.INVARIANT_FORMAT_VERSION if self.hs_kernel == "invariant" else _codec.FORMAT_VERSION
+
+    def _image_format_version(self):
+        return self._format_version()
+
+    def _pack(self, *parts):
+        return self._containers[0](*parts, version=self._format_version())
+
+    def _parse(self, data, abi, compute_dtype):
+        return self._containers[1](data, abi, compute_dtype, version=self._format_version())
+
+    def _pack_image(self, *parts):
+        return self._containers[2](*parts, version=self._image_format_version())
+
+    def _parse_image(self, data, abi, compute_dtype):
+        return self._containers[3](data, abi, compute_dtype, version=self._image_format_version())
 
     def _codable_batch(self):
         self._codable()
@@ -407,7 +439,10 @@ class Compressor2018(nn.Module):
         self.conditional_model._codable()
 
     def _prior_each(self, z_hat):
-        """`_prior` of every image of z_hat on its own (batch shape 1), concatenated."""
+        """`_prior` of every image of z_hat on its own (batch shape 1), concatenated.  Under "invariant" image n's
+        bits do not depend on the batch: one call for all of them."""
+        if self._hs_invariant():
+            return self._prior(z_hat)
         parts = [self._prior(z_hat[n:n + 1]) for n in range(z_hat.shape[0])]
         if len(parts) == 1:
             return parts[0]

@@ -105,14 +105,26 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
 
     # ---- bitstreams: container "ICRC" (codec.py), y as two streams -- the anchors, then the non-anchors.  The format
     # version says which route computed the context, so a stream is only ever decoded by the arithmetic that coded it
+    def _route(self):
+        """What `pack_checkerboard` / `parse_checkerboard` take: the context's route (1 or 2) and whether h_s ran
+        through the batch-invariant kernel."""
+        fused = self.context_kernel == "fused"
+        return dict(version=_codec.CKBD_FUSED_FORMAT_VERSION if fused else _codec.CKBD_FORMAT_VERSION,
+                    invariant=self.hs_kernel == "invariant")
+
     def _format_version(self):
-        return _codec.CKBD_FUSED_FORMAT_VERSION if self.context_kernel == "fused" else _codec.CKBD_FORMAT_VERSION
+        """The number "ICRC" carries: 1 or 2 by the context's route; with h_s by the batch-invariant kernel, 3 or 4."""
+        return _codec.checkerboard_version(**self._route())
+
+    def _image_format_version(self):   # "ICRK" is "fused" only: its version says how h_s ran
+        return (_codec.INVARIANT_FORMAT_VERSION if self.hs_kernel == "invariant"
+                else _codec.CKBD_IMAGE_FORMAT_VERSION)
 
     def _pack(self, *parts):
-        return _codec.pack_checkerboard(*parts, version=self._format_version())
+        return _codec.pack_checkerboard(*parts, **self._route())
 
     def _parse(self, data, abi, compute_dtype):
-        return _codec.parse_checkerboard(data, abi, compute_dtype, version=self._format_version())
+        return _codec.parse_checkerboard(data, abi, compute_dtype, **self._route())
 
     def _codable_batch(self):
         self._codable_each()    # BIN == 1, before anything is computed
@@ -170,7 +182,8 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         (sa, sn) = (_encode_seg(ckbd_gather(y_sym, shape, p), N, ckbd_gather(rows, shape, p), 0, tables_of, ky,
                                 steps_per_chunk) for p in (0, 1))
         return [_codec.pack_checkerboard_image(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w), n),
-                                               sz[n][1], sa[n][1], sn[n][1], sz[n][0], sa[n][0], sn[n][0])
+                                               sz[n][1], sa[n][1], sn[n][1], sz[n][0], sa[n][0], sn[n][0],
+                                               version=self._image_format_version())
                 for n in range(N)]
 
     def _tables_of(self, device):
@@ -190,7 +203,8 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
         chunk size are decoded by the same launches: all their anchors, one context, all their non-anchors, one g_s."""
         self._codable_fused("decompress_each")
         em, cm = self.entropy_model, self.conditional_model
-        parsed = [_codec.parse_checkerboard_image(d, *self._build_id()) for d in streams]   # all validated before any launch
+        parsed = [_codec.parse_checkerboard_image(d, *self._build_id(), version=self._image_format_version())
+                  for d in streams]   # all validated before any launch
         groups = {}
         for m, (h, *_rest) in enumerate(parsed):
             self._check_stream(h, "decompress_each", f"stream {m}")

@@ -166,8 +166,7 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
         return channel_scale(y_hat, self._gains[1])
 
     # ---- bitstreams: containers "ICRG" and "ICRQ" (codec.py)
-    _pack, _parse = staticmethod(_codec.pack_gained), staticmethod(_codec.parse_gained)
-    _pack_image, _parse_image = staticmethod(_codec.pack_gained_image), staticmethod(_codec.parse_gained_image)
+    _containers = (_codec.pack_gained, _codec.parse_gained, _codec.pack_gained_image, _codec.parse_gained_image)
 
     def _codable(self):
         super()._codable()

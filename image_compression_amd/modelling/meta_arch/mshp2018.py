@@ -52,6 +52,9 @@ class MeanScaleCompressor2018(Compressor2018):
 
     def _prior(self, z_hat):
         """(sigma, mu): both heads on the one trunk activation."""
+        if self._hs_invariant():   # the mean head shares the last layer's launch
+            with torch.no_grad():
+                return self.prior_synthesis.invariant(z_hat, second=(self.prior_mean.weight, self.prior_mean.bias))
         t = self.prior_synthesis.trunk(z_hat)
         return self.prior_synthesis.finish(t), self.prior_mean(t)
 

@@ -188,8 +188,7 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
         }
 
     # ---- bitstreams: containers "ICRM" and "ICRR" (codec.py)
-    _pack, _parse = staticmethod(_codec.pack_region), staticmethod(_codec.parse_region)
-    _pack_image, _parse_image = staticmethod(_codec.pack_region_image), staticmethod(_codec.parse_region_image)
+    _containers = (_codec.pack_region, _codec.parse_region, _codec.pack_region_image, _codec.parse_region_image)
 
     def _codable(self):
         super()._codable()

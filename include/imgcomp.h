@@ -613,6 +613,36 @@ int ic_context_fwd(const float* y_in, const float* mu_h, const float* sigma_h, c
                         const float* b_mean, const float* w_scale, const float* b_scale, int N, int H, int W, int C,
                         float* mu, float* sigma, void* ws, size_t ws_bytes, int packed, void* stream);
 
+/* ---- h_s as batch-invariant layers (additive to version 4; csrc/hs_invariant.hip).  One call computes one layer
+ *      ConvTranspose2d(Cin, Cout, k, stride=s, padding=p=k/2, output_padding=s-1, bias) on x: N x H x W x Cin, dense
+ *      channels-last fp32, into out: N x sH x sW x Cout; w: (Cin, Cout, k, k) and b: (Cout) as the module holds them:
+ *          out[n,o,i,j] = b[o] + sum_(ky,kx) sum_c w[c,o,ky,kx] x[n,c,(i+p-ky)/s,(j+p-kx)/s]
+ *      over the taps whose two quotients are exact; a neighbour outside the map contributes a product with +0.0.
+ *      Exact fp32 products with fp32 accumulation (fp32 MFMA) whatever the model's arithmetic.  Every accumulator
+ *      starts from the bias and sums in one order that depends on (k, s, Cin) only: the live taps of the output's
+ *      phase (i % s, j % s) in ascending (ky, kx); inside a tap the channel groups of 8 in ascending order; inside a
+ *      group the channels +0, +4, +1, +5, +2, +6, +3, +7.  No split of K, no atomics, nothing reduced across blocks;
+ *      tiles (32 positions of one phase of one image) are cut per image.  So an output's bits depend on the values
+ *      its taps see, the weights and (k, s, Cin) only: not on N, H, W, the image's index, or its place in the map.
+ *      `epilogue`: IC_HS_NONE; IC_HS_RELU (ic_relu_fwd's bits on the plain output); IC_HS_EXP_CLAMP
+ *      (ic_exp_clamp_fwd's bits: expf, then max with lo, then min with hi).  A second head (w2, b2, epilogue2, out2:
+ *      all null / 0, or all set; same Cout) on the same input runs in the same launch.
+ *      `ws`: 16-byte aligned, at least ic_hs_ws(Cin, Cout, k, s, heads) bytes; it receives the repacked taps, and
+ *      with `packed` != 0 it already holds them (from an earlier call with these weights) and is only read.
+ *      Served: k odd and <= 5, s 1 or 2, 1 <= Cin, Cout <= IC_HS_MAXC.  IC_ERR_ARG before any launch for anything
+ *      else, a null pointer, a size below 1, an unknown epilogue, an element count past 2^63 - 1, or an output of which
+ *      any byte lies in an input, the workspace or the other output; IC_ERR_WORKSPACE for a short workspace.  Neither
+ *      allocates or waits for its stream. ---- */
+#define IC_HS_MAXC 4096
+#define IC_HS_NONE 0
+#define IC_HS_RELU 1
+#define IC_HS_EXP_CLAMP 2
+/* bytes of the packed weights of `heads` (1 or 2) heads; 0: a geometry that is not served */
+size_t ic_hs_ws(int Cin, int Cout, int k, int s, int heads);
+int ic_hs_layer(const float* x, int N, int H, int W, int Cin, int Cout, int k, int s, const float* w, const float* b,
+                int epilogue, float* out, const float* w2, const float* b2, int epilogue2, float* out2, float lo,
+                float hi, void* ws, size_t ws_bytes, int packed, void* stream);
+
 /* ---- gain units (additive to version 4; GainedMeanScaleCompressor2018).  The gain-vector rule: for a table t
  *      (S, C), S >= 2, and a quality q in [0, S-1] held as fp32: s = min((int)floorf(q), S-2), f = q - s,
  *      a = fma(f, t[s+1][c], fl((1-f) t[s][c])): 1-f and the lower level's product rounded once each, the upper

@@ -58,6 +58,11 @@ transcode_each, alternately in one process; with a budget, transcode_each_to bes
 calls; requant_seg beside add_mean + channel_scale x 2 + symbolize_mean_seg on the same operands, by device events; and
 the PSNR and the sizes of both routes beside direct coding at Q2.  --out profiles/codec_transcode_bench.json.
 
+--hs-compare [--budget 450000] runs MODEL.HYPER_SYNTHESIS.KERNEL "conv" and "invariant" alternately on the gained model
+("x32" weights, ladder tables): h_s alone at 1, 8 and 64 maps of z 8 x 12 x 192 by device events (batch-1 conv passes,
+one batched conv pass, one invariant pass), compress_each / decompress_each / compress_each_to at 8 x 3 x 512 x 768 and
+the batch-1 eval forward, compress and decompress; every repetition is kept.  --out profiles/codec_hs_invariant.json.
+
 --context fused|conv builds CheckerboardCompressor2018 with that MODEL.CONTEXT.KERNEL (default conv); with fused,
 --each works on it too (its loop arm is then the fused model's own compress / decompress).
 
@@ -254,9 +259,16 @@ def main():
     ap.add_argument("--rechunk", type=int, default=0, metavar="R", help="steps per chunk of --transcode's outputs")
     ap.add_argument("--transcode-budget", type=int, default=0, metavar="BYTES", dest="transcode_budget",
                     help="with --transcode: transcode_each_to BYTES per stream against the search through pixels")
+    ap.add_argument("--hs-compare", action="store_true", dest="hs_compare",
+                    help='MODEL.HYPER_SYNTHESIS.KERNEL "conv" and "invariant" alternately on the gained model: h_s alone at '
+                         "1, 8 and 64 maps, the per-image calls at 8 x 3 x 512 x 768 (compress_each_to at --budget), the "
+                         "batch-1 calls")
     args = ap.parse_args()
     from image_compression_amd import _lib, codec, get_cfg_defaults, modelling
     from image_compression_amd import functional as F
+    if args.hs_compare:
+        _emit(hs_bench(args), args.out)
+        return
     if args.transcode is not None:
         _emit(transcode_bench(args), args.out)
         return
@@ -368,12 +380,13 @@ def main():
     _emit(tag(out), args.out)
 
 
-def _build(arch, scale, context="conv"):
+def _build(arch, scale, context="conv", hs="conv"):
     from image_compression_amd import get_cfg_defaults, modelling
     cfg = get_cfg_defaults()
     cfg.MODEL.LOSS.REDUCTION = "mean"
     cfg.MODEL.META_ARCHITECTURE = arch
     cfg.MODEL.CONTEXT.KERNEL = context
+    cfg.MODEL.HYPER_SYNTHESIS.KERNEL = hs
     torch.manual_seed(0)
     model = modelling.build_model(cfg).cuda().eval()
     if scale != 1.0:
@@ -1317,6 +1330,79 @@ def transcode_bench(args):
         out["kernels_note"] = ("device events around one call; both symbolizers include their copy of the maxima and their "
                                "stream wait; cache rates, comparable with one another only")
         out["requant_share_of_transcode_each"] = round(out["kernels_ms"]["each"]["requant_seg"] / out["transcode_each_ms"], 4)
+    return out
+
+
+def hs_bench(args):
+    """--hs-compare [--budget BYTES]: the two values of MODEL.HYPER_SYNTHESIS.KERNEL on GainedMeanScaleCompressor2018
+    ("x32" weights, ladder tables, one state dict), alternately rep by rep in one process, inside weight_cache, device
+    synchronised inside the timed region; every repetition is kept.  "conv" is the path of the tree before the switch
+    existed, launch for launch: the yardstick.  h_s alone by device events: M maps of z 8 x 12 x 192 (the latent of
+    512 x 768) as M batch-1 conv passes (what `_prior_each` ran), one batched conv pass, and one invariant pass."""
+    from image_compression_amd import functional as F
+    N, H, W, reps = 8, 512, 768, args.reps
+    budget, Q, rounds, R = args.budget or 450000, args.candidates, args.rounds, 1024
+    g = torch.Generator(device="cuda").manual_seed(5)
+    x = torch.rand(N, 3, H, W, device="cuda", generator=g)
+    x *= torch.linspace(0.25, 1.0, N, device="cuda").view(N, 1, 1, 1)
+    out = {"metric": f"MODEL.HYPER_SYNTHESIS.KERNEL conv | invariant, GainedMeanScaleCompressor2018, {N} x 3 x {H} x {W}, "
+                     f"weight cache, {reps} alternating reps (all kept, best reported)",
+           "unit": "ms", "reps": reps, "weight_scale": 32.0, "budget": budget, "candidates": Q, "rounds": rounds,
+           "data": "synthetic uniform [0,1) images scaled by 0.25 .. 1, resident in HBM; random-init weights (reference "
+                   "init, seed 0), ladder tables +-0.3 per level"}
+
+    def every(fns, timer):
+        """{name: [ms of every rep]} of the functions, alternately."""
+        got = {k: [] for k in fns}
+        for _ in range(reps):
+            for k, fn in fns.items():
+                got[k].append(timer(fn, 1))
+        return got
+
+    def report(got):
+        return {k: {"best": min(v), "worst": max(v), "all": v} for k, v in got.items()}
+
+    with torch.no_grad(), F.weight_cache():
+        models = {}
+        for hs in ("conv", "invariant"):
+            m = _build("GainedMeanScaleCompressor2018", 32.0, hs=hs)[0]
+            for name, sign in (("log_y", 1.0), ("log_inv_y", -1.0), ("log_z", 1.0), ("log_inv_z", -1.0)):
+                getattr(m.gain, name).copy_(sign * 0.3 * torch.arange(m.levels, device="cuda").view(-1, 1))
+            m.set_quality(m.levels - 1)
+            models[hs] = m
+        for p, q in zip(models["conv"].parameters(), models["invariant"].parameters()):
+            assert torch.equal(p, q)
+        conv, inv = models["conv"], models["invariant"]
+        out["h_s"] = {}
+        for M in (1, 8, 64):
+            z = torch.round(torch.randn(M, 192, 8, 12, device="cuda", generator=g) * 3)
+            fns = {"conv_each": lambda: conv._prior_each(z), "conv_batched": lambda: conv._prior(z),
+                   "invariant": lambda: inv._prior_each(z)}
+            for fn in fns.values():
+                fn()
+            out["h_s"][str(M)] = report(every(fns, _events))
+        x1 = x[:1].contiguous()
+        streams = {k: m.compress_each(x, steps_per_chunk=R) for k, m in models.items()}
+        batch1 = {k: m.compress(x1, steps_per_chunk=R) for k, m in models.items()}
+        calls = {
+            "compress_each": lambda k, m: m.compress_each(x, steps_per_chunk=R),
+            "decompress_each": lambda k, m: m.decompress_each(streams[k]),
+            "compress_each_to": lambda k, m: m.compress_each_to(x, budget, steps_per_chunk=R, candidates=Q, rounds=rounds,
+                                                                strict=False),
+            "eval_forward_1": lambda k, m: m(x1),
+            "compress_1": lambda k, m: m.compress(x1, steps_per_chunk=R),
+            "decompress_1": lambda k, m: m.decompress(batch1[k]),
+        }
+        out["calls"] = {}
+        for name, call in calls.items():
+            fns = {k: (lambda k=k, m=m: call(k, m)) for k, m in models.items()}
+            for fn in fns.values():
+                fn()
+            out["calls"][name] = report(every(fns, _wall))
+        out["stream_bytes"] = {k: [len(s) for s in v] for k, v in streams.items()}
+        to = {k: m.compress_each_to(x, budget, steps_per_chunk=R, candidates=Q, rounds=rounds, strict=False)
+              for k, m in models.items()}
+        out["compress_each_to_qualities"] = {k: [float(q) for q in v[1]] for k, v in to.items()}
     return out
 
 
