@@ -280,6 +280,13 @@ SIGNATURES = {
                                   c_void, c_void, c_void, c_void]),
     "ic_block_gain_symbolize_seg": (c_int, [c_void, c_int, c_int, c_int, c_int, c_void, c_int, c_void, c_int, c_void,
                                             c_int, P(c_int), c_void, c_void, c_void, P(c_int), c_void]),
+    # layered per-image streams: the channel energy, the gather into layers and the scatter back (additive to
+    # ic_version 4)
+    "ic_layer_energy": (c_int, [c_void, c_int, c_ll, c_int, c_void, c_void]),
+    "ic_layer_gather": (c_int, [c_void, c_int, c_int, c_ll, c_int, c_int, P(c_int), c_void, P(c_int), c_void, c_int,
+                                c_void, c_void]),
+    "ic_layer_scatter": (c_int, [c_void, c_void, c_int, c_ll, c_int, c_int, P(c_int), c_void, P(c_int), c_void, c_void,
+                                 c_void]),
 }
 
 _lib = None
@@ -311,6 +318,7 @@ transcode_ops = _namespace("imgcomp_transcode", "y's symbols at other qualities 
 alloc_ops = _namespace("imgcomp_alloc", "the per-block level choice and y's symbols under a level map")
 ctx_ops = _namespace("imgcomp_ctx", "the checkerboard context as one batch-invariant kernel")
 hs_ops = _namespace("imgcomp_hs", "h_s as batch-invariant layers, each one launch")
+layer_ops = _namespace("imgcomp_layer", "the channel energy, the gather into layers and the scatter back")
 
 
 def ops():

@@ -299,6 +299,43 @@ neither g_a nor g_s runs.  The formats above are unchanged.
         that already has the target R, in front of any launch; one that has to be re-chunked is judged at its
         re-chunked length, which may fit -- or the stream at quality 0 (for q1 = 0 the stream itself, re-chunked where
         asked): the one result that may exceed its budget.
+
+Layered per-image containers (`Compressor2018.compress_each_layered` / `decompress_each_layered`)
+-------------------------------------------------------------------------------------------------
+A per-image stream whose every byte prefix that holds the tables decodes to an image: y is coded in channel layers, and
+a layer that has not arrived reconstructs as the hyperprior's own prediction.
+    Layers.  y has C channels; they form G layers, 1 <= G <= C, C % G == 0, Cg = C // G.  Each image has a channel
+        order o, a permutation of 0 .. C-1; layer g holds the channels o[g Cg .. (g + 1) Cg - 1], and its symbols are
+        those channels' symbols in (h, w, j) order, j the place inside the layer, fastest.  The symbols are the
+        unchanged ones of `compress_each`: rint(y), rint(y - mu), or on the gained model rint(y * g_y - mu).  Each
+        layer is a bitstream of its own exactly as "Bitstream of one tensor" specifies, its chunks cut from the layer's
+        first symbol; the row of each symbol is index(sigma) at its own (position, channel).  One kmax_y per image
+        serves all layers -- the largest |symbol| of the image, as in "ICRP" -- and so one table.
+    Default order (`layer_order(energy)`).  The channels by descending energy[c] = the sum over positions of symbol^2,
+        an exact integer; ties go to the lower channel index.  Over the layers dropped, this sum is the coded-domain
+        squared error a decoder incurs by putting mu in their place.  It is a steering rule only, and a heuristic: the
+        decoder reads the order from the stream.  order="identity" and an explicit (C,) or (N, C) integer array are
+        accepted (`layer_orders`); anything that is not a permutation is a ValueError before any launch.
+    Absent layers.  A decoder that holds the layers 0 .. L-1 (0 <= L <= G) reconstructs the coded-domain latent as
+        q + mu on their channels -- ic_add_mean's one fp32 addition -- and on all other channels as mu, bit for bit, or
+        +0.0 where the model has no mean.  Then `_latent_ungain` and g_s run as always.  L = 0 is the hyperprior's own
+        picture of the image.
+    Containers.  "ICRL" is the "ICRP" header and "ICRH" the "ICRQ" header (u32 S, f32 quality where "ICRQ" has
+        them), with the field "chunks of y" replaced by "chunks of one layer" (every layer has nsym_y / G symbols and
+        so the same chunk count) and u32 G appended to the fixed header.  After the fixed header: C x u16, the channel
+        order (the variable-length section); then the chunk lengths of z, the chunk lengths of the layers 0 .. G-1, the
+        payload of z, the payloads of the layers 0 .. G-1.  All tables lie in front of all payloads, so any prefix that
+        holds the tables says where every layer ends.  Format version 1, or INVARIANT_FORMAT_VERSION for the h_s
+        route, as in every other per-image container; each route refuses the other's streams.
+    Prefixes.  `layer_ends(data)` = G + 1 byte offsets from the header and the tables alone: ends[0] the end of z's
+        payload, ends[g] the end of layer g-1.  `parse_layered_image(..., prefix=True)` accepts any buffer of at least
+        ends[0] bytes and returns the whole layers it holds, L = max{g : ends[g] <= len(data)}; the bytes of a partly
+        arrived layer are ignored.  Without `prefix` the length must be ends[G] exactly.
+    Refusals (ValueError, before any launch): a buffer that ends inside the header, the order table or the length
+        tables; one shorter than ends[0]; G outside 1 .. C; C % G != 0; an order that is not a permutation; a chunk
+        length that fails the checks of every container.
+The existing parsers refuse the two magics and the two parsers refuse the existing ones: the ten containers do not read
+one another.
 """
 import dataclasses
 import math
@@ -409,12 +446,13 @@ class GainedImageHeader(ImageHeader):
 
 class _MapEq:
     """Equality of the region headers: field by field, the code maps as arrays."""
+    _array_field = "codes"
 
     def __eq__(self, other):
         if type(other) is not type(self):
             return NotImplemented
         a, b = dict(vars(self)), dict(vars(other))
-        ca, cb = a.pop("codes"), b.pop("codes")
+        ca, cb = a.pop(self._array_field), b.pop(self._array_field)
         return a == b and (ca is cb or (ca is not None and cb is not None and np.array_equal(ca, cb)))
 
     __hash__ = None
@@ -438,6 +476,26 @@ class RegionImageHeader(_MapEq, ImageHeader):
     map_h: int
     map_w: int
     codes: np.ndarray = None
+
+
+class _OrderEq(_MapEq):
+    """Equality of the layered headers: field by field, the channel orders as arrays."""
+    _array_field = "order"
+
+
+@dataclass(eq=False)
+class LayeredImageHeader(_OrderEq, ImageHeader):
+    """Header of the layered per-image container: ImageHeader, then the number of layers G and this image's channel
+    order, int32 (latent_channels,)."""
+    layers: int
+    order: np.ndarray = None
+
+
+@dataclass(eq=False)
+class LayeredGainedImageHeader(_OrderEq, GainedImageHeader):
+    """Header of the layered gained per-image container: GainedImageHeader, then the layers and the order."""
+    layers: int
+    order: np.ndarray = None
 
 
 def padded_size(h, w):
@@ -523,6 +581,33 @@ def _pack(head, magic, version, check, h, lens, payloads, extra=(), y_names=("y"
     return b"".join([head.pack(magic, version, *fields), bytes(var)] + [l.tobytes() for l in lens] + payloads)
 
 
+def _parse_header(data, abi, compute_dtype, head, magic, versions, header, check, k):
+    """(checked header object, the k chunk counts, symbols of z, symbols of y) of the fixed header `head` at the start
+    of `data`: the magic, the version (one of `versions`), the arithmetic tag and the ABI against the running build
+    (`abi` None: a reader that decodes nothing checks neither), then `header(common fields, fields after the chunk
+    counts)` passed through `check`."""
+    if len(data) < head.size:
+        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({head.size})")
+    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny,
+     *rest) = head.unpack_from(data, 0)
+    counts, extra = rest[:k], rest[k:]
+    if s_magic != magic:
+        raise ValueError(f"codec: bad magic {s_magic!r}")
+    if ver not in versions:
+        raise ValueError(f"codec: format version {ver}, this build reads {' or '.join(map(str, versions))}")
+    if dt >= len(COMPUTE_DTYPES):
+        raise ValueError(f"codec: unknown arithmetic tag {dt}")
+    if abi is not None:
+        if COMPUTE_DTYPES[dt] != compute_dtype:
+            raise ValueError(f"codec: stream coded with COMPUTE_DTYPE {COMPUTE_DTYPES[dt]!r}, the model runs "
+                             f"{compute_dtype!r}")
+        if s_abi != abi:
+            raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
+    h = header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky, *extra)
+    check(h)
+    return h, counts, nz, ny
+
+
 def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_names=("y",), y_symbols=_whole_y, note="",
            var=None):
     """(header, the streams' chunk-length tables, their payloads) of a container: the header `head` with its magic
@@ -531,25 +616,9 @@ def _parse(data, abi, compute_dtype, head, magic, version, header, check, y_name
     `var` = (size, take): the header has a variable-length section of `size(h)` bytes after its fixed part, which
     `take(h, bytes)` stores in the checked header."""
     data = bytes(data)
-    if len(data) < head.size:
-        raise ValueError(f"codec: {len(data)} bytes is shorter than the header ({head.size})")
     k = 1 + len(y_names)
-    (s_magic, ver, dt, kind, s_abi, N, H, W, cy, cz, L, smin, smax, R, kz, ky, nz, ny,
-     *rest) = head.unpack_from(data, 0)
-    counts, extra = rest[:k], rest[k:]
-    if s_magic != magic:
-        raise ValueError(f"codec: bad magic {s_magic!r}")
-    if ver != version:
-        raise ValueError(f"codec: format version {ver}, this build reads {version}")
-    if dt >= len(COMPUTE_DTYPES):
-        raise ValueError(f"codec: unknown arithmetic tag {dt}")
-    if COMPUTE_DTYPES[dt] != compute_dtype:
-        raise ValueError(f"codec: stream coded with COMPUTE_DTYPE {COMPUTE_DTYPES[dt]!r}, the model runs "
-                         f"{compute_dtype!r}")
-    if s_abi != abi:
-        raise ValueError(f"codec: stream coded by library ABI {s_abi}, this build is {abi}")
-    h = header(N, H, W, cy, cz, kind, COMPUTE_DTYPES[dt], s_abi, L, smin, smax, R, kz, ky, *extra)
-    check(h)
+    h, counts, nz, ny = _parse_header(data, abi, compute_dtype, head, magic, (version,), header, check, k)
+    R = h.R
     nsyms = (h.nsym_z, *y_symbols(h))
     if nz != nsyms[0] or any(len(y_names) * n != ny for n in nsyms[1:]):   # the streams of y hold equal shares of it
         raise ValueError(f"codec: symbol counts do not match the batch shape{note}")
@@ -775,6 +844,194 @@ def parse_gained_image(data, abi, compute_dtype, version=GAINED_FORMAT_VERSION):
     v = _route_version(version, GAINED_FORMAT_VERSION)
     return _parse(data, abi, compute_dtype, _GAINED_IMAGE_HEAD, GAINED_IMAGE_MAGIC, v, GainedImageHeader,
                   _check_gained_image_header)
+
+
+# ---- layered per-image containers "ICRL" and "ICRH": y in G channel layers, any prefix that holds the tables decodes
+LAYERED_IMAGE_MAGIC = b"ICRL"
+LAYERED_GAINED_IMAGE_MAGIC = b"ICRH"
+LAYERED_FORMAT_VERSION = 1
+_LAYERED_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II" + "I")          # the ICRP header, then the layers
+_LAYERED_GAINED_IMAGE_HEAD = struct.Struct(_FIELDS + "II" + "II" + "If" + "I")   # the ICRQ header, then the layers
+MAX_LAYER_CHANNELS = 65535     # the order table holds u16 channel numbers
+
+
+def layer_order(energy):
+    """The default channel order from energy (C,) or (N, C), non-negative integers (the sum over positions of
+    symbol^2): the channels by descending energy, ties to the lower channel index; int32, the shape of `energy`."""
+    e = np.asarray(energy)
+    if e.dtype.kind not in "iu" or e.ndim not in (1, 2) or e.shape[-1] < 1 or (e.size and e.min() < 0):
+        raise ValueError(f"codec: the energies are non-negative integers (C,) or (N, C), got {e.dtype} {e.shape}")
+    if e.size and int(e.max()) > np.iinfo(np.int64).max:
+        raise ValueError("codec: an energy beyond 2^63")
+    return np.argsort(-e.astype(np.int64), axis=-1, kind="stable").astype(np.int32)
+
+
+def _check_order(order, C):
+    o = np.asarray(order)
+    if o.dtype.kind not in "iu" or o.shape != (C,) or not np.array_equal(np.sort(o.astype(np.int64)), np.arange(C)):
+        raise ValueError(f"codec: a channel order is a permutation of 0 .. {C - 1}")
+
+
+def layer_orders(order, N, C):
+    """int32 (N, C): the channel order of every image of a call from `order` = "identity", a (C,) array for all of
+    them or an (N, C) array.  ValueError for anything that is not a permutation of 0 .. C-1 per image."""
+    if isinstance(order, str):
+        if order != "identity":
+            raise ValueError(f"codec: order is 'energy', 'identity' or an integer array, got {order!r}")
+        return np.tile(np.arange(C, dtype=np.int32), (N, 1))
+    o = np.asarray(order)
+    if o.dtype.kind not in "iu" or o.shape not in ((C,), (N, C)):
+        raise ValueError(f"codec: an explicit order is an integer array ({C},) or ({N}, {C}), got {o.dtype} {o.shape}")
+    o = np.broadcast_to(o, (N, C))
+    for row in o:
+        _check_order(row, C)
+    return np.ascontiguousarray(o, dtype=np.int32)
+
+
+def _check_layers(h):
+    C, G = h.latent_channels, h.layers
+    if C > MAX_LAYER_CHANNELS:
+        raise ValueError(f"codec: a layered stream numbers at most {MAX_LAYER_CHANNELS} channels, got {C}")
+    if isinstance(G, bool) or int(G) != G or not 1 <= G <= C:
+        raise ValueError(f"codec: {G} layers of {C} channels (1 .. {C})")
+    if C % G:
+        raise ValueError(f"codec: {G} layers do not divide {C} channels")
+    if h.order is not None:
+        _check_order(h.order, C)
+
+
+def _check_layered_image_header(h):
+    _check_image_header(h)
+    _check_layers(h)
+
+
+def _check_layered_gained_image_header(h):
+    _check_gained_image_header(h)
+    _check_layers(h)
+
+
+# (fixed header, magic, header class, its check, the header fields after the chunk counts) of the two containers
+_LAYERED = {
+    False: (_LAYERED_IMAGE_HEAD, LAYERED_IMAGE_MAGIC, LayeredImageHeader, _check_layered_image_header,
+            lambda h: (h.height, h.width, h.layers)),
+    True: (_LAYERED_GAINED_IMAGE_HEAD, LAYERED_GAINED_IMAGE_MAGIC, LayeredGainedImageHeader,
+           _check_layered_gained_image_header, lambda h: (h.height, h.width, h.levels, h.quality, h.layers)),
+}
+
+
+def _layer_symbols(h):
+    return h.nsym_y // h.layers
+
+
+def layered_image_fixed_bytes(h):
+    """`fixed_bytes` of a layered per-image container (either kind, by the header's type), the order table included."""
+    head = _LAYERED[isinstance(h, LayeredGainedImageHeader)][0]
+    nc = num_chunks(h.nsym_z, h.R) + h.layers * num_chunks(_layer_symbols(h), h.R)
+    return head.size + 2 * h.latent_channels + 4 * nc + CHUNK_HEAD * nc
+
+
+def _pack_layered(gained, h, lens_z, lens_layers, payload_z, payload_layers, version):
+    head, magic, cls, check, extra = _LAYERED[gained]
+    v = _route_version(version, LAYERED_FORMAT_VERSION)
+    if type(h) is not cls:
+        raise ValueError(f"codec: this container takes a {cls.__name__}, not a {type(h).__name__}")
+    check(h)
+    if h.order is None:
+        raise ValueError("codec: a layered header without its channel order")
+    lens = [np.ascontiguousarray(l, dtype="<u4") for l in (lens_z, *lens_layers)]
+    payloads = [bytes(p) for p in (payload_z, *payload_layers)]
+    if len(lens) != h.layers + 1 or len(payloads) != h.layers + 1:
+        raise ValueError(f"codec: {len(lens) - 1} length tables and {len(payloads) - 1} payloads for {h.layers} layers")
+    _check_lengths("z", lens[0], h.nsym_z, h.R)
+    for g, l in enumerate(lens[1:]):
+        _check_lengths(f"y layer {g}", l, _layer_symbols(h), h.R)
+    if any(int(l.sum(dtype=np.uint64)) != len(p) for l, p in zip(lens, payloads)):
+        raise ValueError("codec: chunk lengths do not add up to the payload")
+    fields = (COMPUTE_DTYPES.index(h.compute_dtype), h.kind, h.abi, h.N, h.H, h.W, h.latent_channels, h.hyper_channels,
+              h.L, h.scale_min, h.scale_max, h.R, h.kmax_z, h.kmax_y, h.nsym_z, h.nsym_y, len(lens[0]), len(lens[1]),
+              *extra(h))
+    order = np.ascontiguousarray(h.order, dtype="<u2").tobytes()
+    return b"".join([head.pack(magic, v, *fields), order] + [l.tobytes() for l in lens] + payloads)
+
+
+def _layered_layout(data, gained, abi, compute_dtype, versions):
+    """(header, [the length table of z, of layer 0, ..], [ends[0], .., ends[G]]) of a layered container or of a prefix
+    of one that holds the header, the order table and the length tables; nothing behind the tables is read."""
+    head, magic, cls, check, _ = _LAYERED[gained]
+    h, counts, nz, ny = _parse_header(data, abi, compute_dtype, head, magic, versions, cls, check, 2)
+    if nz != h.nsym_z or ny != h.nsym_y:
+        raise ValueError("codec: symbol counts do not match the image shape")
+    nsyms = (h.nsym_z, _layer_symbols(h))
+    if any(c != num_chunks(n, h.R) for c, n in zip(counts, nsyms)):
+        raise ValueError("codec: chunk counts do not match the symbol counts")
+    off, C, G = head.size, h.latent_channels, h.layers
+    if len(data) < off + 2 * C:
+        raise ValueError(f"codec: buffer ends inside the channel order of {2 * C} bytes")
+    order = np.frombuffer(data, dtype="<u2", count=C, offset=off).astype(np.int32)
+    _check_order(order, C)
+    h.order = order
+    off += 2 * C
+    if len(data) < off + 4 * (counts[0] + G * counts[1]):
+        raise ValueError("codec: buffer ends inside the chunk-length tables")
+    tables = []
+    for g in range(G + 1):
+        c = counts[min(g, 1)]
+        tables.append(np.frombuffer(data, dtype="<u4", count=c, offset=off))
+        off += 4 * c
+        _check_lengths("z" if g == 0 else f"y layer {g - 1}", tables[-1], nsyms[min(g, 1)], h.R)
+    ends = (off + np.cumsum([int(t.sum(dtype=np.uint64)) for t in tables], dtype=np.int64)).tolist()
+    return h, tables, [off, *ends]
+
+
+def _parse_layered(data, gained, abi, compute_dtype, version, prefix):
+    v = _route_version(version, LAYERED_FORMAT_VERSION)
+    data = bytes(data)
+    h, tables, (first, *ends) = _layered_layout(data, gained, abi, compute_dtype, (v,))
+    if prefix:
+        if len(data) < ends[0]:
+            raise ValueError(f"codec: a prefix of {len(data)} bytes ends in front of the end of z's payload at {ends[0]}")
+        held = max(g for g in range(h.layers + 1) if ends[g] <= len(data))
+    else:
+        if len(data) != ends[-1]:
+            raise ValueError(f"codec: the tables put the stream's end at {ends[-1]} bytes, the buffer holds {len(data)}")
+        held = h.layers
+    return (h, tables[0], tables[1:], data[first:ends[0]], [data[ends[g]:ends[g + 1]] for g in range(held)])
+
+
+def pack_layered_image(h, lens_z, lens_layers, payload_z, payload_layers, version=LAYERED_FORMAT_VERSION):
+    """One bytes object for one image from its LayeredImageHeader, the length table of z, those of the G layers, the
+    payload of z and those of the G layers."""
+    return _pack_layered(False, h, lens_z, lens_layers, payload_z, payload_layers, version)
+
+
+def parse_layered_image(data, abi, compute_dtype, version=LAYERED_FORMAT_VERSION, prefix=False):
+    """(LayeredImageHeader, lens_z, [lens of layer g for all G], payload_z, [payload of layer g for the L layers held])
+    of a container made by `pack_layered_image`.  Without `prefix` the buffer is the whole stream and L = G; with it,
+    any prefix of at least `layer_ends(data)[0]` bytes, L the whole layers it holds.  Nothing is launched here."""
+    return _parse_layered(data, False, abi, compute_dtype, version, prefix)
+
+
+def pack_layered_gained_image(h, lens_z, lens_layers, payload_z, payload_layers, version=LAYERED_FORMAT_VERSION):
+    """`pack_layered_image` for a LayeredGainedImageHeader."""
+    return _pack_layered(True, h, lens_z, lens_layers, payload_z, payload_layers, version)
+
+
+def parse_layered_gained_image(data, abi, compute_dtype, version=LAYERED_FORMAT_VERSION, prefix=False):
+    """`parse_layered_image` for a container made by `pack_layered_gained_image`: the checks of the levels and the
+    quality besides."""
+    return _parse_layered(data, True, abi, compute_dtype, version, prefix)
+
+
+def layer_ends(data):
+    """[ends[0], .., ends[G]] of a layered stream ("ICRL" or "ICRH", either format version) or of any prefix of it that
+    holds the header, the order table and the length tables: ends[0] is the end of z's payload and ends[g] the end of
+    layer g-1, in bytes from the stream's start.  The build that decodes is not consulted: nothing is decoded here."""
+    data = bytes(data)
+    magics = {LAYERED_IMAGE_MAGIC: False, LAYERED_GAINED_IMAGE_MAGIC: True}
+    if data[:4] not in magics:
+        raise ValueError(f"codec: bad magic {data[:4]!r}")
+    versions = (LAYERED_FORMAT_VERSION, INVARIANT_FORMAT_VERSION)
+    return _layered_layout(data, magics[data[:4]], None, None, versions)[2][1:]
 
 
 # ---- coding to a byte budget: the search rule of `compress_each_to` (the docstring's last section)

@@ -2482,6 +2482,121 @@ Tensor window_crop_clamp_at_meta(const Tensor& x, int64_t top, int64_t left, int
   return at::empty({x.size(0), x.size(1), h, w}, x.options().memory_format(at::MemoryFormat::Contiguous));
 }
 
+// ---------------------------------------------------------------- layered per-image streams (imgcomp_layer)
+// The dense side is (N, P, C), channel fastest; order holds N rows of C channel numbers and G layers share them.
+// Shapes and counts are checked here (and by the Meta kernels); every entry of order, seg and nlayers by the C entry
+// points, before anything is launched.
+void check_layer_counts(int64_t N, int64_t P, int64_t C, int64_t G, int64_t order_size) {
+  TORCH_CHECK(N >= 1 && N <= INT_MAX && P >= 1 && C >= 1 && C <= INT_MAX && P <= (INT64_MAX / 8) / C / N,
+              "imgcomp_layer: (N, P, C) = (", N, ", ", P, ", ", C, ") is empty or too large");
+  TORCH_CHECK(G >= 1 && G <= C && C % G == 0, "imgcomp_layer: ", G, " layers do not divide ", C, " channels");
+  TORCH_CHECK(order_size == N * C, "imgcomp_layer: order holds ", order_size, " entries, not N C = ", N * C);
+}
+
+void check_layer_dense(const Tensor& t, const char* what) {
+  TORCH_CHECK(t.dim() == 3 && t.is_contiguous() && t.numel() > 0, "imgcomp_layer: ", what,
+              " must be a non-empty contiguous (N, P, C) tensor, got ", t.sizes());
+}
+
+std::vector<int> layer_ints(at::IntArrayRef v, const char* what) {
+  std::vector<int> out(v.size());
+  for (size_t i = 0; i < v.size(); ++i) {
+    TORCH_CHECK(v[i] >= INT_MIN && v[i] <= INT_MAX, "imgcomp_layer: entry ", i, " of ", what, " is not an int");
+    out[i] = (int)v[i];
+  }
+  return out;
+}
+
+int64_t check_layer_gather(const Tensor& src, int64_t G, at::IntArrayRef order, at::IntArrayRef seg) {
+  check_layer_dense(src, "src");
+  const auto ty = src.scalar_type();
+  TORCH_CHECK(ty == at::kByte || ty == at::kInt || ty == at::kFloat, "imgcomp_layer: src must be uint8, int32 or float32, got ",
+              ty);
+  check_layer_counts(src.size(0), src.size(1), src.size(2), G, (int64_t)order.size());
+  const int64_t nseg = (int64_t)seg.size() / 2;
+  TORCH_CHECK(nseg >= 1 && nseg <= 65535 && (int64_t)seg.size() == 2 * nseg,
+              "imgcomp_layer: seg holds (image, layer) for each of 1 .. 65535 segments, got ", seg.size(), " integers");
+  return nseg;
+}
+
+void check_layer_scatter(const Tensor& q, const std::optional<Tensor>& mu, int64_t N, int64_t P, int64_t C, int64_t G,
+                         at::IntArrayRef order, at::IntArrayRef nlayers) {
+  check_layer_counts(N, P, C, G, (int64_t)order.size());
+  TORCH_CHECK((int64_t)nlayers.size() == N, "imgcomp_layer: nlayers holds ", nlayers.size(), " entries, not N = ", N);
+  int64_t sum = 0;
+  for (int64_t v : nlayers) {
+    TORCH_CHECK(v >= 0 && v <= G, "imgcomp_layer: an image brings 0 .. ", G, " layers, got ", v);
+    sum += v;
+  }
+  TORCH_CHECK(q.scalar_type() == at::kFloat && q.numel() == sum * P * (C / G), "imgcomp_layer: q must hold the ", sum,
+              " layers present as float32, ", sum * P * (C / G), " values, got ", q.numel(), " of ", q.scalar_type());
+  if (mu.has_value() && mu->defined()) {
+    check_layer_dense(*mu, "mu");
+    TORCH_CHECK(mu->scalar_type() == at::kFloat && mu->size(0) == N && mu->size(1) == P && mu->size(2) == C,
+                "imgcomp_layer: mu must be float32 (", N, ", ", P, ", ", C, "), got ", mu->sizes());
+  }
+}
+
+Tensor layer_energy(const Tensor& sym) {
+  check_layer_dense(sym, "sym");
+  check_codec(sym, at::kInt, "sym");
+  const int64_t N = sym.size(0), P = sym.size(1), C = sym.size(2);
+  check_layer_counts(N, P, C, 1, N * C);
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(sym.device());
+  Tensor energy = at::empty({N, C}, sym.options().dtype(at::kLong));
+  check_rc(ic_layer_energy(sym.data_ptr<int>(), (int)N, P, (int)C, (unsigned long long*)energy.data_ptr<int64_t>(),
+                           stream_of(sym)),
+           "layer_energy");
+  return energy;
+}
+
+Tensor layer_gather(const Tensor& src, int64_t G, at::IntArrayRef order, at::IntArrayRef seg) {
+  const int64_t nseg = check_layer_gather(src, G, order, seg);
+  TORCH_CHECK(src.is_cuda(), "imgcomp_layer: src must be on a ROCm device, got ", src.device());
+  const int64_t N = src.size(0), P = src.size(1), C = src.size(2);
+  const std::vector<int> ord = layer_ints(order, "order"), sg = layer_ints(seg, "seg");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(src.device());
+  Tensor dst = at::empty({nseg * P * (C / G)}, src.options());
+  Tensor ints = at::empty({N * C + 4 * nseg + N + 1}, src.options().dtype(at::kInt));
+  int* dev = ints.data_ptr<int>();
+  check_rc(ic_layer_gather(src.data_ptr(), (int)src.element_size(), (int)N, P, (int)C, (int)G, ord.data(), dev, sg.data(),
+                           dev + N * C, (int)nseg, dst.data_ptr(), stream_of(src)),
+           "layer_gather");
+  return dst;
+}
+
+Tensor layer_scatter(const Tensor& q, const std::optional<Tensor>& mu, int64_t N, int64_t P, int64_t C, int64_t G,
+                     at::IntArrayRef order, at::IntArrayRef nlayers) {
+  check_layer_scatter(q, mu, N, P, C, G, order, nlayers);
+  const bool hm = mu.has_value() && mu->defined();
+  TORCH_CHECK(q.is_cuda() && q.is_contiguous(), "imgcomp_layer: q must be contiguous on a ROCm device, got ", q.device());
+  TORCH_CHECK(!hm || mu->device() == q.device(), "imgcomp_layer: mu must be on q's device");
+  const std::vector<int> ord = layer_ints(order, "order"), nl = layer_ints(nlayers, "nlayers");
+  const c10::hip::OptionalHIPGuardMasqueradingAsCUDA guard(q.device());
+  Tensor y_hat = at::empty({N, P, C}, q.options());
+  Tensor ints = at::empty({N * C + 2 * N}, q.options().dtype(at::kInt));
+  int* dev = ints.data_ptr<int>();
+  check_rc(ic_layer_scatter(q.numel() ? q.data_ptr<float>() : nullptr, hm ? mu->data_ptr<float>() : nullptr, (int)N, P,
+                            (int)C, (int)G, ord.data(), dev, nl.data(), dev + N * C, y_hat.data_ptr<float>(),
+                            stream_of(q)),
+           "layer_scatter");
+  return y_hat;
+}
+
+Tensor layer_energy_meta(const Tensor& sym) {
+  check_layer_dense(sym, "sym");
+  return at::empty({sym.size(0), sym.size(2)}, sym.options().dtype(at::kLong));
+}
+Tensor layer_gather_meta(const Tensor& src, int64_t G, at::IntArrayRef order, at::IntArrayRef seg) {
+  const int64_t nseg = check_layer_gather(src, G, order, seg);
+  return at::empty({nseg * src.size(1) * (src.size(2) / G)}, src.options());
+}
+Tensor layer_scatter_meta(const Tensor& q, const std::optional<Tensor>& mu, int64_t N, int64_t P, int64_t C, int64_t G,
+                          at::IntArrayRef order, at::IntArrayRef nlayers) {
+  check_layer_scatter(q, mu, N, P, C, G, order, nlayers);
+  return at::empty({N, P, C}, q.options());
+}
+
 }  // namespace
 
 TORCH_LIBRARY(imgcomp, m) {
@@ -2942,6 +3057,26 @@ TORCH_LIBRARY(imgcomp_transcode, m) {
 TORCH_LIBRARY_IMPL(imgcomp_transcode, CUDA, m) { m.impl("requant_seg", transcode_requant_seg); }
 
 TORCH_LIBRARY_IMPL(imgcomp_transcode, Meta, m) { m.impl("requant_seg", transcode_requant_seg_meta); }
+
+// Layered per-image streams (Compressor2018.compress_each_layered / decompress_each_layered): additive, in a namespace
+// of its own.  Inference only: no autograd node.
+TORCH_LIBRARY(imgcomp_layer, m) {
+  m.def("energy(Tensor sym) -> Tensor");
+  m.def("gather(Tensor src, int layers, int[] order, int[] seg) -> Tensor");
+  m.def("scatter(Tensor q, Tensor? mu, int N, int P, int C, int layers, int[] order, int[] nlayers) -> Tensor");
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_layer, CUDA, m) {
+  m.impl("energy", layer_energy);
+  m.impl("gather", layer_gather);
+  m.impl("scatter", layer_scatter);
+}
+
+TORCH_LIBRARY_IMPL(imgcomp_layer, Meta, m) {
+  m.impl("energy", layer_energy_meta);
+  m.impl("gather", layer_gather_meta);
+  m.impl("scatter", layer_scatter_meta);
+}
 
 // Choosing a quality map under a byte budget (RegionGainedMeanScaleCompressor2018.compress_each_map_to): additive, in a
 // namespace of its own.  Inference only: no autograd node.

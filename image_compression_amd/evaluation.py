@@ -17,6 +17,8 @@ Kodak evaluator and its metrics, on HIP kernels.
   bits of the real bitstream per pixel, beside the estimated `bpp`.
 * `rd_sweep(model, batches, qualities)` — one `run_eval` per quality of a model with gain units
   (GainedMeanScaleCompressor2018): the rate-distortion ladder of one checkpoint.
+* `progressive_sweep(model, batches)` — one `compress_each_layered` per batch, then one decode per number of layers
+  held: the bits per pixel and the PSNR of every prefix of the layered streams.
 """
 import contextlib
 import ctypes
@@ -180,6 +182,38 @@ def rd_sweep(model, batches, qualities, coded=True, **evaluator_args):
     finally:
         model.set_quality(before)
     return results
+
+
+def progressive_sweep(model, batches, layers=8, order="energy", steps_per_chunk=1024, device=None):
+    """The prefix-quality curve of the layered streams (`compress_each_layered`): every batch (N, 3, h, w) is coded
+    once, then decoded G + 1 times, from the prefixes that hold L = 0 .. G layers.  Returns G + 1 dicts
+    {"layers": L, "bpp": the mean over images of 8 * ends[L] / (h w), "psnr": the mean per-image PSNR in dB}; the
+    last row is the whole stream.  The curve is only as good as the layer order, a heuristic."""
+    from . import codec
+    was_training = model.training
+    model.eval()
+    bpp = psnr_sum = None
+    count = 0
+    try:
+        for imgs in batches:
+            if device is not None:
+                imgs = imgs.to(device, non_blocking=True)
+            streams = model.compress_each_layered(imgs, layers=layers, order=order, steps_per_chunk=steps_per_chunk)
+            ends = [codec.layer_ends(s) for s in streams]
+            G = len(ends[0]) - 1
+            if bpp is None:
+                bpp, psnr_sum = [0.0] * (G + 1), [0.0] * (G + 1)
+            n_pix = imgs.shape[2] * imgs.shape[3]
+            for L in range(G + 1):
+                x_hat = torch.cat(model.decompress_each_layered([s[:e[L]] for s, e in zip(streams, ends)]))
+                psnr_sum[L] += float(psnr(x_hat, imgs).double().sum())
+                bpp[L] += sum(8.0 * e[L] / n_pix for e in ends)
+            count += len(streams)
+    finally:
+        model.train(was_training)
+    if not count:
+        raise ValueError("progressive_sweep: no images")
+    return [{"layers": L, "bpp": bpp[L] / count, "psnr": psnr_sum[L] / count} for L in range(len(bpp))]
 
 
 class Evaluator:

@@ -123,6 +123,8 @@ class Compressor2018(nn.Module):
         self.loss_names = ["y_entropy", "z_entropy", "bpp"] + list(self.distortion_loss_fns.keys())
         # g_s's taps and strides: what a pixel of the output depends on (decompress_window)
         self._synthesis_geometry = (int(cfg.MODEL.CONV_KERNEL), tuple(int(s) for s in cfg.MODEL.STRIDES))
+        # y's channels: what the layers of a layered stream divide (compress_each_layered)
+        self._latent_channels = int(cfg.MODEL.LATENT_CHANNELS)
         # the hyperprior branch (h_a, factorized model, h_s, the y likelihood) on a second
         # stream, concurrent with the synthesis transform (see forward)
         self.concurrent_hyperprior = True
@@ -501,6 +503,133 @@ class Compressor2018(nn.Module):
             for m, img in zip(idx, self._reconstruct_each(y_hat, hs)):
                 out[m] = img
         return out
+
+    # ---- layered per-image streams: y coded in channel layers, any prefix that holds the tables decodes (containers
+    # "ICRL" / "ICRH"; codec.py states the rule).  A layer is a segment of the segmented coder; a layer that has not
+    # arrived reconstructs as mu, the hyperprior's own prediction.
+    layered_refusal = None    # a model whose y is not one bitstream under (sigma, mu) = h_s(z_hat) says why here
+    _layered_containers = (_codec.pack_layered_image, _codec.parse_layered_image, _codec.LayeredImageHeader)
+
+    def _check_layered(self, who):
+        if self.layered_refusal:
+            raise ValueError(f"{who}: {self.layered_refusal}")
+        self._codable_each()
+
+    @torch.no_grad()
+    def compress_each_layered(self, x, layers=8, order="energy", steps_per_chunk=1024):
+        """x (N, 3, h, w) in [0, 1], any h, w >= 1 -> a list of N bytes objects, one layered stream per image: the
+        symbols of `compress_each`, y's channels in `layers` layers, each a bitstream of its own behind all tables, so
+        that `decompress_each_layered` reads any prefix that holds the tables (codec.py: "Layered per-image
+        containers").  order: "energy" (the channels by descending sum of symbol^2, per image: a steering heuristic
+        that the decoder reads from the stream, never recomputes), "identity", or an integer array (C,) or (N, C)."""
+        who = "compress_each_layered"
+        self._check_layered(who)
+        em, cm = self.entropy_model, self.conditional_model
+        C, G = self._latent_channels, layers
+        if isinstance(G, bool) or not isinstance(G, (int, np.integer)) or not 1 <= G <= C or C % G:
+            raise ValueError(f"{who}: layers is an integer in [1, {C}] that divides the {C} latent channels, got {G!r}")
+        G = int(G)
+        if x.dim() == 4 and x.shape[0] * G > 65535:
+            raise ValueError(f"{who}: {x.shape[0]} images in {G} layers are more than 65535 segments")
+        energy = isinstance(order, str) and order == "energy"
+        if not energy and x.dim() == 4:
+            try:
+                orders = _codec.layer_orders(order, x.shape[0], C)     # in front of any launch
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+        pack, _parse, header = self._layered_containers
+        x, (N, h, w, H, W) = self._pad_each(x)
+        y, z, z_sym, kz, (sigma, mean) = self._analyse(x, each=True)
+        y_sym, ky = self._symbols(self._latent_gain(y), mean, each=True)
+        if y.shape[1] != C:
+            raise ValueError(f"{who}: the latent has {y.shape[1]} channels, the model's configuration says {C}")
+        P = y.shape[2] * y.shape[3]
+        sym = y_sym.view(N, P, C)
+        ops = _lib.layer_ops()
+        if energy:
+            orders = _codec.layer_order(ops.energy(sym).cpu().numpy())    # the one small copy: (N, C) integers
+        flat_order = orders.reshape(-1).tolist()
+        seg = [v for n in range(N) for g in range(G) for v in (n, g)]
+        rows = cm.scale_rows(sigma.expand_as(y)).view(N, P, C)
+        sz = em.encode_symbols_seg(z_sym, kz, steps_per_chunk)
+        sy = _encode_seg(ops.gather(sym, G, flat_order, seg), N * G, ops.gather(rows, G, flat_order, seg), 0,
+                         lambda K: cm.tables(K, y.device), [k for k in ky for _ in range(G)], steps_per_chunk)
+        out = []
+        for n in range(N):
+            hd = header(**vars(self._header(1, H, W, y, z, steps_per_chunk, kz[n], ky[n], (h, w), n)), layers=G,
+                        order=orders[n].copy())
+            mine = sy[n * G:(n + 1) * G]
+            out.append(pack(hd, sz[n][1], [l for _, l in mine], sz[n][0], [p for p, _ in mine],
+                            version=self._image_format_version()))
+        return out
+
+    def _layered_latents(self, streams, layers, who):
+        """Parses and checks everything, then for every group of streams that share (H, W, C, R, G) yields
+        ([m], their headers, the coded-domain latent (len([m]), C, Hy, Wy) in front of `_latent_ungain`), with
+        `_begin_decode` done for the group: the caller finishes a group before it asks for the next."""
+        self._check_layered(who)
+        em, cm = self.entropy_model, self.conditional_model
+        if isinstance(streams, (bytes, bytearray, memoryview, str)):
+            raise ValueError(f"{who}: `streams` is a list of layered streams, not one {type(streams).__name__}")
+        streams = list(streams)
+        caps = list(layers) if isinstance(layers, (list, tuple, np.ndarray)) else [layers] * len(streams)
+        if len(caps) != len(streams):
+            raise ValueError(f"{who}: {len(caps)} layer counts for {len(streams)} streams")
+        for cap in caps:
+            if cap is not None and (isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or cap < 0):
+                raise ValueError(f"{who}: layers is None or an integer >= 0 (one for all streams or one each), got {cap!r}")
+        parse = self._layered_containers[1]
+        parsed, held, groups = [], [], {}
+        for m, d in enumerate(streams):     # everything is validated before any launch
+            parsed.append(parse(d, *self._build_id(), version=self._image_format_version(), prefix=True))
+            h = parsed[-1][0]
+            self._check_stream(h, who, f"stream {m}")
+            held.append(len(parsed[-1][4]) if caps[m] is None else min(len(parsed[-1][4]), int(caps[m])))
+            groups.setdefault((h.H, h.W, h.latent_channels, h.R, h.layers), []).append(m)
+        for idx in groups.values():
+            if sum(held[m] for m in idx) > 65535:
+                raise ValueError(f"{who}: {sum(held[m] for m in idx)} layers of one shape are more than 65535 segments")
+        ops = _lib.layer_ops()
+        for (_H, _W, C, R, G), idx in groups.items():
+            hs = [parsed[m][0] for m in idx]
+            self._begin_decode(hs)
+            z_hat = em.decompress_seg([parsed[m][3] for m in idx], hs[0].z_shape, [parsed[m][1] for m in idx],
+                                      [h.kmax_z for h in hs], R)
+            sigma, mean = self._prior_each(self._hyper_ungain(z_hat))
+            if tuple(sigma.shape[1:]) != hs[0].y_shape[1:]:
+                raise ValueError(f"{who}: the model's sigma {tuple(sigma.shape)} is not the streams' latent shape "
+                                 f"{hs[0].y_shape}")
+            n, (_, _, Hy, Wy) = len(idx), hs[0].y_shape
+            P, Cg = Hy * Wy, C // G
+            flat_order = np.concatenate([h.order for h in hs]).tolist()
+            nl = [held[m] for m in idx]
+            seg = [v for k in range(n) for g in range(nl[k]) for v in (k, g)]
+            if seg:
+                rows = ops.gather(cm.scale_rows(sigma).view(n, P, C), G, flat_order, seg)
+                q = _decode_seg([parsed[m][4][g] for k, m in enumerate(idx) for g in range(nl[k])],
+                                [parsed[m][2][g] for k, m in enumerate(idx) for g in range(nl[k])], P * Cg, rows, 0,
+                                lambda K: cm.tables(K, sigma.device), [h.kmax_y for k, h in enumerate(hs) for _ in range(nl[k])],
+                                R, sigma.device)
+            else:
+                q = torch.empty(0, dtype=torch.float32, device=sigma.device)
+            mu = None if mean is None else _to_last(mean).view(n, P, C)
+            flat = ops.scatter(q, mu, n, P, C, G, flat_order, nl)
+            yield idx, hs, symbols_as_tensor(flat.view(-1), (n, C, Hy, Wy))
+
+    @torch.no_grad()
+    def decompress_each_layered(self, streams, layers=None):
+        """A list of M layered streams from `compress_each_layered`, each whole or any prefix that holds its tables
+        (`codec.layer_ends(data)[0]` bytes at least) -> a list of M tensors (1, 3, h_m, w_m).  A stream decodes from
+        the whole layers its bytes hold, at most `layers` of them (None: all; an int, or one per stream); the channels
+        of every other layer reconstruct as mu, the hyperprior's prediction (+0.0 on the scale hyperprior), and
+        `layers=0` is the hyperprior's own picture of the image.  Everything is parsed and checked before any launch;
+        streams that share a padded size, a chunk size and a layer count pass the same launches, whatever each
+        holds.  The quality of the prefixes comes from the layer order, a heuristic measured on untrained weights."""
+        out = {}
+        for idx, hs, y_hat in self._layered_latents(streams, layers, "decompress_each_layered"):
+            for m, img in zip(idx, self._reconstruct_each(self._latent_ungain(y_hat), hs)):
+                out[m] = img
+        return [out[m] for m in range(len(out))]
 
     # ---- a pixel window of a per-image stream: only the chunks that hold its latent rows are decoded and g_s runs on the
     # latent window alone (codec.py states the plan).  The streams are `compress_each`'s, unchanged.

@@ -57,6 +57,8 @@ class CheckerboardCompressor2018(MeanScaleCompressor2018):
 
     refine_refusal = ("CheckerboardCompressor2018 is not covered: the non-anchors' (sigma, mu) depend on y, so moving y "
                       "moves the decoder's inputs")
+    layered_refusal = ("CheckerboardCompressor2018 is not covered: the non-anchors' (sigma, mu) come from the decoded "
+                       "anchors of every channel, so a channel layer cannot be decoded, or left out, on its own")
     window_refusal = ("CheckerboardCompressor2018 is not covered: y is coded as two gathered halves, anchors and "
                       "non-anchors, so a band of latent rows is not a range of chunks, and the non-anchors' (sigma, mu) "
                       "need the anchors around them")

@@ -167,6 +167,8 @@ class GainedMeanScaleCompressor2018(MeanScaleCompressor2018):
 
     # ---- bitstreams: containers "ICRG" and "ICRQ" (codec.py)
     _containers = (_codec.pack_gained, _codec.parse_gained, _codec.pack_gained_image, _codec.parse_gained_image)
+    _layered_containers = (_codec.pack_layered_gained_image, _codec.parse_layered_gained_image,
+                           _codec.LayeredGainedImageHeader)
 
     def _codable(self):
         super()._codable()

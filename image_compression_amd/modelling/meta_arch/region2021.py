@@ -57,6 +57,8 @@ class RegionGainedMeanScaleCompressor2018(GainedMeanScaleCompressor2018):
                      "step: a captured graph would replay one map for ever; use TrainStep(graph=False)")
     refine_refusal = ("RegionGainedMeanScaleCompressor2018 is not covered: its distortion is weighed by a quality map, "
                       "which the objective R + lambda MSE does not know; use GainedMeanScaleCompressor2018")
+    layered_refusal = ("RegionGainedMeanScaleCompressor2018 is not covered: the layered containers carry one quality "
+                       "per image, not a quality map; use GainedMeanScaleCompressor2018")
 
     def __init__(self, cfg):
         names, reduction = list(cfg.MODEL.LOSS.DISTORTION_LOSS_NAMES), cfg.MODEL.LOSS.REDUCTION
